@@ -4,6 +4,8 @@
 
     python bench.py --gpus N --steps K --warmup W            (the driver's contract)
     python bench.py --method svgd --gpus N ...               (BASELINE.json configs[4]: 64 particles sharded over N GPUs)
+    python bench.py ... --full                               (+ the roofline / phase and cpu_baseline legs below)
+    python bench.py ... --dump-outputs DIR                   (+ what the last timed step computed, as DIR/<name>.npy)
 
 A step = one pass of the hot path over one batch: forward, loss, backward, fused
 noise + parameter + moment update (Pyesian/optimizers/SGLD.py:46-95).  Inputs
@@ -15,7 +17,9 @@ Everything one-time (graph capture for every chunk length a run of K or W steps 
 before the warm-up; `config.path` says what the timed region really executed (read back from the
 library: steps inside replayed hipGraphs / eager steps / graph launches).
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the optional
+output dump, the JSON line.  With --full, extra objects on the JSON line (measured after the timed
+region and the dump, so neither changes the headline nor the dumped outputs):
   roofline      the dominant kernel of the step (the slowest of k_dense_fwd, k_head_rows,
                 k_wgrad_all): algorithmic FLOP per launch / its average duration.  Durations are
                 measured live, after the timed region and independently of it: 256 further steps of
@@ -25,6 +29,13 @@ Extra objects on the JSON line:
                 command must agree).
   cpu_baseline  the oracle's eager torch-CPU restatement of the same step
                 (oracle/torch_eager.py, kind "port") on the host cores.
+  (--method svgd: roofline with the per-phase HIP-event times, phases_us_per_rank, cpu_baseline.)
+
+--dump-outputs DIR writes, on rank 0, the arrays a caller of the timed path holds after its last step:
+SGLD theta, mean, sq_mean (float32, D each) and that step's loss; SVGD the particle matrix gathered over
+the ranks, as a fixed sample of its columns (the (64, D) matrix is 41 MB; see SVGD_DUMP_COLUMNS), and the
+summed loss.  The inputs depend on the arguments only, so two builds run with the same arguments can be
+compared array for array.
 """
 
 from __future__ import annotations
@@ -51,6 +62,8 @@ BYTES_PER_STEP = 7.03e6
 SVGD_M, SVGD_LR = 64, 0.01     # BASELINE.json configs[4]; SVGD_mnist.py:11
 SVGD_FLOP_PER_STEP = 45.2e9    # 41.9 gradients + 1.95 kernel + 1.3 repulsion
 PMC_TRAFFIC = "r03_pmc_traffic.json"
+DUMP_LIMIT_BYTES = 64 << 20
+SVGD_DUMP_COLUMNS = 32768      # parameters per particle in the SVGD dump: sorted, drawn once with default_rng(0)
 
 
 def cpu_model() -> str:
@@ -174,6 +187,20 @@ def timed_region(run_warm, run_timed, world, backend, dev):
     return dt
 
 
+def dump_outputs(dirname, arrays):
+    """Writes every (name, tensor) of `arrays` as dirname/<name>.npy in float32 (float64 stays float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: outputs of {total} bytes exceed the dump limit of {DUMP_LIMIT_BYTES}")
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def whole_step(flop, nbytes, step_us):
     tf = flop / (step_us * 1e-6) / 1e12
     return {"flop": flop, "bytes": nbytes, "us": round(step_us, 3), "tflops": round(tf, 3),
@@ -234,10 +261,12 @@ def bench_sgld(args, rank, world, backend, dev):
     plan.check_finite()                                # PYZ_E_NAN if any step of the run produced a NaN / Inf loss
     if not np.isfinite(last_loss):
         raise SystemExit(f"bench.py: non-finite loss {last_loss} on rank {rank}")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"theta": theta, "mean": mean, "sq_mean": sq_mean, "loss": losses[total - 1:total]})
 
     roof = None
     step_us = dt / args.steps * 1e6
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # Per-kernel durations, measured independently of the timed region: 256 further steps of the same chain,
         # launched eagerly back to back, every kernel with its own start / stop event pair.
         n_prof = 256
@@ -296,7 +325,7 @@ def bench_sgld(args, rank, world, backend, dev):
                        "parallelism": f"independent chains x{args.gpus} (replicas only, no data-path collective)"},
             "roofline": roof,
         }
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             out["cpu_baseline"] = cpu_baseline()
     return out
 
@@ -443,40 +472,49 @@ def bench_svgd(args, rank, world, backend, dev):
     parallel.sum_over_ranks(total_loss)
     step_us = dt / args.steps * 1e6
 
-    # ---- after the timed region, independently of it: where a step's time goes on THIS rank (HIP events per phase; the
-    #      gather's share shows which all-gather algorithm RCCL picked: ~33 us direct, ~233 us ring for 5 MB per rank over
-    #      7 x ~153 GB/s xGMI links), and the kernels of one step with their own begin / end timestamps
-    ev = {k: [] for k in ("gather", "gradients", "kernel_matrix", "tail", "step")}
-    for s in range(total, total + 12):
-        one_step(s, ev)
-    torch.cuda.synchronize()
-    phases = {k: round(float(np.median([a.elapsed_time(b) * 1e3 for a, b in v])), 1) for k, v in ev.items() if v}
-    with engine.KernelProbe(512) as kp:
-        for s in range(total + 12, total + 16):
-            one_step(s)
-    per = {n: (c / 4.0, us) for n, (c, us) in kp.by_kernel().items()}
-    B, K1, N1, N2 = BATCH, DIMS[0], DIMS[1], DIMS[2]
-    f_fwd = 2.0 * B * (K1 + 1) * N1 * n_local
-    flop_of = {"k_dense_fwd": f_fwd, "k_dense_fwd_lds": f_fwd, "k_dense_fwd_ring": f_fwd,
-               "k_wgrad_all": f_fwd + 2.0 * B * (N1 + 1) * N2 * n_local,
-               "k_head_rows": (2.0 * B * (N1 + 1) * N2 + 2.0 * B * N1 * N2) * n_local}
-    kern = {n: (c, us, flop_of[n.split("<")[0]]) for n, (c, us) in per.items() if n.split("<")[0] in flop_of}
-    roof = {"bound": "mfma", "whole_step": whole_step(SVGD_FLOP_PER_STEP, 247e6, step_us),
-            "phases_us_rank0": phases,
-            "kernels_us_per_step": {n: [round(c, 2), round(us, 2)] for n, (c, us) in sorted(per.items(), key=lambda kv: -kv[1][0] * kv[1][1])}}
-    if kern:
-        k = max(kern, key=lambda n: kern[n][0] * kern[n][1])
-        c, us_k, fl = kern[k]
-        achieved = fl / (us_k * 1e-6) / 1e12
-        roof.update({"kernel": k, "kernel_us": round(us_k, 3), "flop_per_launch": fl, "achieved": round(achieved, 3),
-                     "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
-                     "traffic": None,
-                     "timing": "start/stop event pair per launch (hipExtLaunchKernelGGL), 4 eager steps after the timed region"})
-    all_phases = [phases]
-    if world > 1:
-        gathered = [None] * world
-        dist.all_gather_object(gathered, phases)
-        all_phases = gathered
+    if args.dump_outputs:
+        if sharded:                                   # every rank's rows of the last step into the full matrix
+            parallel.all_gather_rows(buf["local"], buf["all"])
+        if rank == 0:
+            cols = np.sort(np.random.default_rng(0).choice(D, SVGD_DUMP_COLUMNS, replace=False))
+            dump_outputs(args.dump_outputs, {"particles": buf["all"][:, torch.as_tensor(cols, device=dev)], "loss": total_loss})
+
+    roof = all_phases = None
+    if args.full:
+        # ---- after the timed region, independently of it: where a step's time goes on THIS rank (HIP events per phase; the
+        #      gather's share shows which all-gather algorithm RCCL picked: ~33 us direct, ~233 us ring for 5 MB per rank over
+        #      7 x ~153 GB/s xGMI links), and the kernels of one step with their own begin / end timestamps
+        ev = {k: [] for k in ("gather", "gradients", "kernel_matrix", "tail", "step")}
+        for s in range(total, total + 12):
+            one_step(s, ev)
+        torch.cuda.synchronize()
+        phases = {k: round(float(np.median([a.elapsed_time(b) * 1e3 for a, b in v])), 1) for k, v in ev.items() if v}
+        with engine.KernelProbe(512) as kp:
+            for s in range(total + 12, total + 16):
+                one_step(s)
+        per = {n: (c / 4.0, us) for n, (c, us) in kp.by_kernel().items()}
+        B, K1, N1, N2 = BATCH, DIMS[0], DIMS[1], DIMS[2]
+        f_fwd = 2.0 * B * (K1 + 1) * N1 * n_local
+        flop_of = {"k_dense_fwd": f_fwd, "k_dense_fwd_lds": f_fwd, "k_dense_fwd_ring": f_fwd,
+                   "k_wgrad_all": f_fwd + 2.0 * B * (N1 + 1) * N2 * n_local,
+                   "k_head_rows": (2.0 * B * (N1 + 1) * N2 + 2.0 * B * N1 * N2) * n_local}
+        kern = {n: (c, us, flop_of[n.split("<")[0]]) for n, (c, us) in per.items() if n.split("<")[0] in flop_of}
+        roof = {"bound": "mfma", "whole_step": whole_step(SVGD_FLOP_PER_STEP, 247e6, step_us),
+                "phases_us_rank0": phases,
+                "kernels_us_per_step": {n: [round(c, 2), round(us, 2)] for n, (c, us) in sorted(per.items(), key=lambda kv: -kv[1][0] * kv[1][1])}}
+        if kern:
+            k = max(kern, key=lambda n: kern[n][0] * kern[n][1])
+            c, us_k, fl = kern[k]
+            achieved = fl / (us_k * 1e-6) / 1e12
+            roof.update({"kernel": k, "kernel_us": round(us_k, 3), "flop_per_launch": fl, "achieved": round(achieved, 3),
+                         "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
+                         "traffic": None,
+                         "timing": "start/stop event pair per launch (hipExtLaunchKernelGGL), 4 eager steps after the timed region"})
+        all_phases = [phases]
+        if world > 1:
+            gathered = [None] * world
+            dist.all_gather_object(gathered, phases)
+            all_phases = gathered
     if rank != 0:
         return None
     out = {
@@ -496,9 +534,10 @@ def bench_svgd(args, rank, world, backend, dev):
                    "parallelism": (f"particles sharded x{args.gpus} ({n_local} per GPU), one all-gather of the (64, D) matrix "
                                    "per step" if world > 1 else "1 GPU, no collective")},
         "roofline": roof,
-        "phases_us_per_rank": all_phases,
     }
-    if not args.no_cpu_baseline and args.gpus == 1:
+    if args.full:
+        out["phases_us_per_rank"] = all_phases
+    if args.full and not args.no_cpu_baseline and args.gpus == 1:
         out["cpu_baseline"] = cpu_baseline_svgd()
     return out
 
@@ -513,6 +552,10 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel timing (used for the PMC passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / phases and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 4000 if args.method == "sgld" else 100

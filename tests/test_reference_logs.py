@@ -1,5 +1,5 @@
 """Statistical pin against the ONLY outputs the reference holds for this path: the grid-search logs under
-/root/reference/logs (rows copied as numbers into tests/golden/reference_logs.json, with line numbers).
+the reference's logs/ (rows copied as numbers into tests/golden/reference_logs.json, with line numbers).
 
 The logs are single unseeded runs per row (test-set accuracy on 200 rows / MSE on 60 rows), so what can be
 asserted is coarse: bands and orderings over the means of a few seeded replays.  What this pins:
