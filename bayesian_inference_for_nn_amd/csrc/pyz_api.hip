@@ -206,8 +206,10 @@ void launch_loss(pyz_mlp *m, int P, const void *y, const int32_t *row_idx, int g
 
 inline int loss_nblk(const pyz_mlp *m, int grid_batch) { return std::min(cdiv(m->max_batch, 256), cdiv(grid_batch, 256)); }
 
+// grad_sq (one chain only): the weight-gradient kernels also write the batch mean of the squared per-example gradients there
 void launch_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, const float *x,
-                     const int32_t *row_idx, int grid_batch, const StepCtl *ctl, float *grad, hipStream_t st) {
+                     const int32_t *row_idx, int grid_batch, const StepCtl *ctl, float *grad, hipStream_t st,
+                     float *grad_sq = nullptr) {
   for (int l = m->L - 1; l >= 0; --l) {
     const int K = m->dims[l], N = m->dims[l + 1];
     if (l > 0) {  // delta[l-1] = (delta[l] W_l^T) * act'(h_{l-1})
@@ -247,7 +249,8 @@ void launch_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, 
     g.out_pstride = m->D;
     g.w_off = m->w_off[l];
     g.ctl = ctl;
-    pyz_launch_bwd_weight(g, grid_batch, P, st);
+    if (grad_sq) pyz_launch_bwd_weight_sq(g, grad_sq, grid_batch, st);
+    else pyz_launch_bwd_weight(g, grid_batch, P, st);
   }
 }
 
@@ -371,9 +374,9 @@ inline int wgrad_tiles(const pyz_mlp *m) {   // workgroups of k_wgrad_all that o
   return tiles;
 }
 
-// every layer's weight gradient in one launch; `a` carries the update mode and its buffers
-void launch_wgrad_all(pyz_mlp *m, int P, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl,
-                      WgradArgs &a, hipStream_t st, const float *gathered) {
+// the layers, tiles and duties of a weight-gradient launch (k_wgrad_all, k_wgrad_adam); returns the tile count
+int wgrad_layers(pyz_mlp *m, int P, const float *x, const int32_t *row_idx, const StepCtl *ctl, WgradArgs &a,
+                 const float *gathered) {
   int tiles = 0;
   a.L = m->L;
   for (int l = 0; l < m->L; ++l) {
@@ -403,6 +406,13 @@ void launch_wgrad_all(pyz_mlp *m, int P, const float *x, const int32_t *row_idx,
   a.tiles = tiles;
   a.nonfinite = m->nonfinite;
   a.wt = pyz_wt_for(P);
+  return tiles;
+}
+
+// every layer's weight gradient in one launch; `a` carries the update mode and its buffers
+void launch_wgrad_all(pyz_mlp *m, int P, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl,
+                      WgradArgs &a, hipStream_t st, const float *gathered) {
+  const int tiles = wgrad_layers(m, P, x, row_idx, ctl, a, gathered);
   const int S = pyz_pick_waves((long long)tiles * P, (grid_batch + 1) / 2);
   dim3 grid(pyz_pad8((long long)tiles + 1, P), P);  // + the duties workgroup (+ padding, see pyz_pad8)
   if (a.prep.src && P == 1) grid.x = (unsigned)(tiles + 1 + std::max(pyz_cu_count() - tiles - 1, 24));  // + the batch workers
@@ -415,6 +425,21 @@ void launch_wgrad_all(pyz_mlp *m, int P, const float *x, const int32_t *row_idx,
     case 4: PYZ_LAUNCH(k_wgrad_all<4>, grid, dim3(256), 4 * 4096, st, a); break;
     case 8: PYZ_LAUNCH(k_wgrad_all<8>, grid, dim3(512), 8 * 4096, st, a); break;
     default: PYZ_LAUNCH(k_wgrad_all<16>, grid, dim3(1024), 16 * 4096, st, a); break;
+  }
+}
+
+// ADAM / VADAM (one chain): every layer's gradient and squared-gradient mean, and the update, in one launch
+void launch_wgrad_adam(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl, AdamArgs &a,
+                       hipStream_t st, const float *gathered) {
+  const int tiles = wgrad_layers(m, 1, x, row_idx, ctl, a.w, gathered);
+  const int S = pyz_pick_waves(tiles, (grid_batch + 1) / 2);
+  const dim3 grid(tiles + 1);   // + the duties workgroup
+  switch (S) {
+    case 1: PYZ_LAUNCH(k_wgrad_adam<1>, grid, dim3(64), 0, st, a); break;
+    case 2: PYZ_LAUNCH(k_wgrad_adam<2>, grid, dim3(128), 2 * 4096, st, a); break;
+    case 4: PYZ_LAUNCH(k_wgrad_adam<4>, grid, dim3(256), 4 * 4096, st, a); break;
+    case 8: PYZ_LAUNCH(k_wgrad_adam<8>, grid, dim3(512), 8 * 4096, st, a); break;
+    default: PYZ_LAUNCH(k_wgrad_adam<16>, grid, dim3(1024), 16 * 4096, st, a); break;
   }
 }
 
@@ -464,9 +489,11 @@ int ksplit_for(pyz_mlp *m, const float *theta, long long theta_ps, int P, const 
   return ks_env;
 }
 
+// adam (one chain, no ahead_slot): the weight-gradient launch is k_wgrad_adam with a.w = upd (fused path), or the
+// squared-gradient kernels write their means to grad2 beside upd.grad (unfused path)
 void launch_loss_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, const float *x, const void *y,
                           const int32_t *row_idx, int grid_batch, const StepCtl *ctl, bool want_grad, WgradArgs &upd,
-                          hipStream_t st, int ahead_slot = -1) {
+                          hipStream_t st, int ahead_slot = -1, AdamArgs *adam = nullptr) {
   if (can_fuse(m)) {
     if (ahead_slot >= 0) {
       const float *xc = batch_buf(m, ahead_slot);
@@ -494,7 +521,8 @@ void launch_loss_backward(pyz_mlp *m, const float *theta, long long theta_ps, in
     launch_head(m, theta, theta_ps, P, x, y, row_idx, grid_batch, ctl, want_grad, st);
     if (want_grad) {
       launch_bwd_data_hidden(m, theta, theta_ps, P, grid_batch, ctl, st);
-      launch_wgrad_all(m, P, x, row_idx, grid_batch, ctl, upd, st, xb);
+      if (adam) launch_wgrad_adam(m, x, row_idx, grid_batch, ctl, *adam, st, xb);
+      else launch_wgrad_all(m, P, x, row_idx, grid_batch, ctl, upd, st, xb);
     }
     return;
   }
@@ -502,7 +530,7 @@ void launch_loss_backward(pyz_mlp *m, const float *theta, long long theta_ps, in
   launch_forward(m, theta, theta_ps, P, x, row_idx, grid_batch, ctl, st);
   launch_loss(m, P, y, row_idx, grid_batch, ctl, want_grad, st);
   m->cur_nblk = loss_nblk(m, grid_batch);
-  if (want_grad) launch_backward(m, theta, theta_ps, P, x, row_idx, grid_batch, ctl, upd.grad, st);
+  if (want_grad) launch_backward(m, theta, theta_ps, P, x, row_idx, grid_batch, ctl, upd.grad, st, adam ? m->grad2 : nullptr);
 }
 
 int check_loss_combo(const pyz_mlp *m) {
@@ -512,6 +540,21 @@ int check_loss_combo(const pyz_mlp *m) {
   if (m->loss == PYZ_LOSS_MSE && last == PYZ_ACT_SOFTMAX)
     return pyz_fail(PYZ_E_INVALID, "MeanSquaredError on a softmax last layer is not supported");
   return PYZ_OK;
+}
+
+// the update's scalars, each computed in float64 and rounded to float32 once (see AdamScal)
+AdamScal adam_scalars(float lr, double beta_1, double beta_2, long long epoch, float denom_eps, float decay) {
+  AdamScal a;
+  a.lr = lr;
+  a.b1 = (float)beta_1;
+  a.c1 = (float)(1.0 - beta_1);
+  a.b2 = (float)beta_2;
+  a.c2 = (float)(1.0 - beta_2);
+  a.bc1 = (float)(1.0 - std::pow(beta_1, (double)epoch));
+  a.bc2 = (float)(1.0 - std::pow(beta_2, (double)epoch));
+  a.eps = denom_eps;
+  a.decay = decay;
+  return a;
 }
 
 }  // namespace
@@ -715,6 +758,53 @@ int pyz_sgd_step(pyz_mlp *m, float *d_theta, const float *d_x, const void *d_y, 
   if (!fused)
     PYZ_LAUNCH(k_sgd_update, dim3(cdiv(m->D, 256)), dim3(256), 0, st, d_theta, m->grad, m->D, m->ctl, m->part,
                        m->cur_nblk, d_loss, m->nonfinite);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- ADAM (ADAM.py:42-86) / VADAM (VADAM.py:44-98)
+int pyz_adam_step(pyz_mlp *m, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                  const int32_t *d_row_idx, int batch, float lr, double beta_1, double beta_2, int64_t epoch,
+                  float denom_eps, float decay, float *d_loss, void *stream) {
+  int rc = check_call(m, 1, batch);
+  if (rc) return rc;
+  if ((rc = check_loss_combo(m))) return rc;
+  if (!d_theta || !d_m || !d_v || !d_x || !d_y || !d_loss) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (epoch < 1) return pyz_fail(PYZ_E_INVALID, "epoch %lld < 1", (long long)epoch);
+  if (!(beta_1 >= 0.0 && beta_1 < 1.0) || !(beta_2 >= 0.0 && beta_2 < 1.0))
+    return pyz_fail(PYZ_E_INVALID, "beta_1 = %g, beta_2 = %g: both must lie in [0, 1)", beta_1, beta_2);
+  const bool fused = can_fuse(m);
+  if (!fused && ((rc = need_grad(m, 1)) || (rc = need_grad2(m, 1)))) return rc;
+  hipStream_t st = as_stream(stream);
+  set_ctl_lazy(m, batch, lr, 0);
+  AdamArgs a{};
+  a.w.mode = PYZ_UPD_NONE;
+  a.m = d_m;
+  a.v = d_v;
+  a.a = adam_scalars(lr, beta_1, beta_2, epoch, denom_eps, decay);
+  if (fused) {  // gradients, squared-gradient means and the update in one weight-gradient launch
+    a.w.theta = d_theta;
+    a.w.loss = d_loss;
+  } else {
+    a.w.grad = m->grad;
+    a.w.grad_pstride = m->D;
+  }
+  launch_loss_backward(m, d_theta, m->D, 1, d_x, d_y, d_row_idx, batch, m->ctl, true, a.w, st, -1, &a);
+  if (!fused)
+    PYZ_LAUNCH(k_adam_update, dim3(cdiv(m->D, 256)), dim3(256), 0, st, d_theta, d_m, d_v, m->grad, m->grad2, m->D, a.a,
+               m->ctl, m->part, m->cur_nblk, d_loss, m->nonfinite);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_vadam_perturb(pyz_mlp *m, float *d_theta, const float *d_v, float lam, float num_data, int64_t step, uint64_t seed,
+                      const float *d_eps, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (!d_theta || !d_v) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (!(num_data > 0.0f)) return pyz_fail(PYZ_E_INVALID, "num_data = %g must be positive", (double)num_data);
+  if (step < 0) return pyz_fail(PYZ_E_INVALID, "negative step");
+  PYZ_LAUNCH(k_vadam_perturb, dim3(cdiv(cdiv(m->D, 4), 256)), dim3(256), 0, as_stream(stream), d_theta, d_v, m->D, lam,
+             num_data, seed, (uint32_t)step, d_eps);
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
 }

@@ -1003,3 +1003,185 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_all(WgradArgs g) {
   }
   PYZ_STAMP(2, 3);
 }
+
+// pyz_wgrad_accumulate with a second chain: acc2 += (a^2) (fb d)^2 from the masked operands of every step (k_wgrad_adam)
+template <class H>
+__device__ __forceinline__ void pyz_wgrad_accumulate_sq(f32x16 &acc, f32x16 &acc2, const float fb, const float *abase,
+                                                        const int ic, const float *dbase, const int n, const int lda,
+                                                        const int N, const int batch, int s, const int se, const int h,
+                                                        const bool is_w, const bool is_b, H hook) {
+  const float bconst = is_b ? 1.0f : 0.0f;
+  const unsigned a_lane = ((unsigned)h * (unsigned)lda + (unsigned)ic) * 4u;
+  const unsigned d_lane = ((unsigned)h * (unsigned)N + (unsigned)n) * 4u;
+  const unsigned a_row2 = 8u * (unsigned)lda, d_row2 = 8u * (unsigned)N;  // bytes per MFMA step (two rows)
+  const __amdgpu_buffer_rsrc_t ra =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(abase), 0, (int)((unsigned)batch * (unsigned)lda * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(dbase), 0, (int)((unsigned)batch * (unsigned)N * 4u), 0x00020000);
+  // only whole steps here: the scalar offset is not range checked, so the odd last row is peeled
+  const int full = batch >> 1;
+  pyz_steps1_all(
+      s, min(se, full), acc,
+      [&](int st, float &a, float &d) {
+        a = pyz_buf_load(ra, a_lane, (unsigned)PYZ_HOT(st, batch) * a_row2);
+        d = pyz_buf_load(rd, d_lane, (unsigned)PYZ_HOT(st, batch) * d_row2);
+      },
+      [&](int, float &a, float &d) {
+        a = is_w ? a : bconst;
+        const float gd = d * fb;
+        acc2 = pyz_mfma(a * a, gd * gd, acc2);
+      },
+      hook);
+  if (se > full) {  // this wave owns the odd last row: the second reduction slot of its MFMA stays empty
+    const int b = batch - 1;
+    float a = abase[(size_t)b * lda + ic], d = dbase[(size_t)b * N + n];
+    a = h == 0 ? (is_w ? a : bconst) : 0.0f;
+    d = h == 0 ? d : 0.0f;
+    const float gd = d * fb;
+    acc2 = pyz_mfma(a * a, gd * gd, acc2);
+    acc = pyz_mfma(a, d, acc);
+  }
+}
+
+// ---------------------------------------------------------------- ADAM / VADAM: gradients, their second moment, update
+// ADAM.step / VADAM.step need per parameter the batch mean g of the per-example gradients and the batch mean s of their
+// squares (the reference squares a (B, D) tape.jacobian: ADAM.py:60-75, VADAM.py:67-96).  For a Dense layer the
+// per-example gradient of [W; b] is a_i (x) (B delta_i) -- delta carries the 1/B of the mean loss (k_head) -- so
+//     s = (1/B) (A o A)^T ((B Delta) o (B Delta)),
+// the reduction over the batch that k_wgrad_all runs for A^T Delta, on squared operands: a second MFMA chain beside the
+// first, fed from the registers the operands were loaded into (no Jacobian, no second pass over the activations).
+// Scaling: delta is multiplied by B BEFORE it is squared, so the chain sums squares of per-example gradients (what the
+// reference squares) and only the final sum is divided by B; squaring delta itself (g^2 / B^2) would send every
+// per-example gradient below ~1e-19 * B through the float32 subnormals.  B is the step's batch (ctl->batch: the last batch
+// of an epoch is shorter).  The two tiles are combined across waves through the same `red` buffer, one after the other.
+// A kernel of its own (not a mode of k_wgrad_all): the SGD / SGLD / SWAG / BBB / PLAIN instantiations are left as they were.
+struct AdamArgs {
+  WgradArgs w;   // layers, tiles, theta, the duties (loss, nonfinite); mode PYZ_UPD_NONE, grad unused
+  float *m, *v;
+  AdamScal a;
+};
+
+template <int S>
+__global__ void __launch_bounds__(64 * S) k_wgrad_adam(AdamArgs A) {
+  extern __shared__ float red[];
+  const WgradArgs &g = A.w;
+  constexpr int EPT = 16 / S;  // tile elements per thread in the epilogue
+  const int w = pyz_wave_id(), l = threadIdx.x & 63;
+  const int r = l & 31, h = l >> 5;
+  if (blockIdx.x >= (unsigned)g.tiles) {  // the duties workgroup: the step's loss and the non-finite count
+    if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    return;
+  }
+  const int tile = pyz_xcd_remap(blockIdx.x, g.tiles);
+  int li = 0;
+  while (li + 1 < g.L && tile >= g.lay[li + 1].tile0) ++li;
+  const WgradLayer &ly = g.lay[li];
+  const int batch = g.ctl->batch;
+  const int K = ly.K, N = ly.N;
+  const int tiles_n = (N + 31) >> 5;
+  const int t = tile - ly.tile0;
+  const int i0 = (t / tiles_n) * 32, n0 = (t % tiles_n) * 32;
+  const long long w_off = ly.w_off;
+
+  // the state of this thread's elements, fetched behind the first group of operand loads (see k_wgrad_all)
+  long long ee[EPT];
+  bool ev[EPT];
+  float th0[EPT], m0[EPT], v0[EPT];
+  auto prefetch = [&]() {
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      int ro, co;
+      if (S == 1) {
+        ro = (q & 3) + 8 * (q >> 2) + 4 * h;
+        co = r;
+      } else {
+        const int e = threadIdx.x + q * 64 * S;
+        ro = e >> 5;
+        co = e & 31;
+      }
+      const int ii = i0 + ro, nn = n0 + co;
+      ev[q] = ii <= K && nn < N;
+      ee[q] = w_off + (long long)min(ii, K) * N + min(nn, N - 1);
+      th0[q] = g.theta[ee[q]];
+      m0[q] = A.m[ee[q]];
+      v0[q] = A.v[ee[q]];
+    }
+  };
+
+  const int i = i0 + r, n = min(n0 + r, N - 1);
+  const int ic = min(i, K - 1);
+  const bool is_w = i < K, is_b = i == K;
+  const float *ap = ly.in + ic;
+  const float *dp = ly.delta + n;
+  const int32_t *idx = (ly.gather && g.row_idx) ? g.row_idx + g.ctl->row_off : nullptr;
+  const float fb = (float)batch;
+  f32x16 acc = {0}, acc2 = {0};
+  const int steps = (batch + 1) >> 1;
+  int s = (steps * w) / S;
+  const int se = (steps * (w + 1)) / S;
+  if (idx) {
+    prefetch();
+    for (int s0 = s; s0 < se; s0 += 32) {   // gathered rows: k_wgrad_all's index broadcast
+      const int idxv = idx[min(2 * s0 + l, batch - 1)];
+      const int lda = ly.lda;
+      pyz_steps1_all(
+          s0, min(s0 + 32, se), acc,
+          [&](int st, float &a, float &d) {
+            const int bc = min(2 * st + h, batch - 1);
+            const long long row = __shfl(idxv, 2 * (st - s0) + h, 64);
+            a = ap[row * lda];
+            d = dp[(long long)bc * N];
+          },
+          [&](int st, float &a, float &d) {
+            const bool vb = 2 * st + h < batch;
+            a = vb ? (is_w ? a : (is_b ? 1.0f : 0.0f)) : 0.0f;
+            d = vb ? d : 0.0f;
+            const float gd = d * fb;
+            acc2 = pyz_mfma(a * a, gd * gd, acc2);
+          });
+    }
+  } else {
+    pyz_wgrad_accumulate_sq(acc, acc2, fb, ly.in, ic, ly.delta, n, ly.lda, N, batch, s, se, h, is_w, is_b, prefetch);
+  }
+  float gv[EPT], sv[EPT];
+  if (S == 1) {
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      gv[q] = acc[q];
+      sv[q] = acc2[q];
+    }
+  } else {
+    float *my = red + w * 1024;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) my[((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + r] = acc[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      const int e = threadIdx.x + q * 64 * S;
+      float v = red[e];
+#pragma unroll
+      for (int ww = 1; ww < S; ++ww) v += red[ww * 1024 + e];
+      gv[q] = v;
+    }
+    __syncthreads();   // every wave has read the first round
+#pragma unroll
+    for (int q = 0; q < 16; ++q) my[((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + r] = acc2[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      const int e = threadIdx.x + q * 64 * S;
+      float v = red[e];
+#pragma unroll
+      for (int ww = 1; ww < S; ++ww) v += red[ww * 1024 + e];
+      sv[q] = v;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < EPT; ++q) {
+    if (!ev[q]) continue;
+    const PyzAdamOut o = pyz_adam_math(A.a, th0[q], m0[q], v0[q], gv[q], sv[q] / fb);
+    pyz_st(g.theta + ee[q], o.th, g.wt);
+    pyz_st(A.m + ee[q], o.m, g.wt);
+    pyz_st(A.v + ee[q], o.v, g.wt);
+  }
+}

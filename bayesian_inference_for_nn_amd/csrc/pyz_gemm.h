@@ -572,10 +572,12 @@ __global__ void k_dense_bwd_data(DenseArgs g) {
 // With a row gather, the 32 row indices of a 16-step group are fetched by ONE
 // coalesced load (lane j holds the index of batch row 2*s0 + j) and handed to the
 // step that needs them with a lane permute, so no load depends on another load.
-template <int G, bool GATHER>
+// SQ: a second chain acc2 += (a^2) (dsc d)^2 beside the first (k_dense_bwd_weight_sq).
+template <int G, bool GATHER, bool SQ = false>
 __device__ __forceinline__ void pyz_wgrad_steps(int &s, const int se, f32x16 &acc, const float *ap, const float *dp,
                                                 const int32_t *idx, const int lda, const int N, const int batch,
-                                                const int h, const int r, const bool is_w, const bool is_b) {
+                                                const int h, const int r, const bool is_w, const bool is_b,
+                                                f32x16 *acc2 = nullptr, const float dsc = 0.0f) {
   for (; s + G <= se; s += G) {
     float a[G], d[G];
     int idxv = 0;
@@ -597,6 +599,10 @@ __device__ __forceinline__ void pyz_wgrad_steps(int &s, const int se, f32x16 &ac
       const bool vb = 2 * (s + u) + h < batch;
       const float av = vb ? (is_w ? a[u] : (is_b ? 1.0f : 0.0f)) : 0.0f;
       acc = pyz_mfma(av, vb ? d[u] : 0.0f, acc);
+      if constexpr (SQ) {
+        const float gd = (vb ? d[u] : 0.0f) * dsc;
+        *acc2 = pyz_mfma(av * av, gd * gd, *acc2);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -635,6 +641,52 @@ __global__ void k_dense_bwd_weight(DenseArgs g) {
   pyz_tile_epilogue(acc, red, [&](int ro, int co, float v) {
     const int ii = i0 + ro, nn = n0 + co;
     if (ii <= K && nn < N) op[(long long)ii * N + nn] = v;
+  });
+}
+
+// k_dense_bwd_weight plus the batch mean of the squared per-example gradients (ADAM.py:60-75, VADAM.py:67-96 square a
+// tape.jacobian): the per-example gradient of [W; b] is a_i (x) (B delta_i) -- delta carries the 1/B of the mean loss --
+// so a second chain sums (a_i^2) (x) (B delta_i)^2 and out2 receives that sum / B.  delta is scaled by B BEFORE it is
+// squared: the chain sums squares of per-example gradients, as the reference does, instead of delta^2 = g^2 / B^2, which
+// would send gradients below ~1e-19 * B through the float32 subnormals.  B = the step's batch.
+__global__ void k_dense_bwd_weight_sq(DenseArgs g, float *out2) {
+  extern __shared__ float red[];
+  const int S = blockDim.x >> 6, w = pyz_wave_id(), l = threadIdx.x & 63;
+  const int r = l & 31, h = l >> 5;
+  const int batch = g.ctl->batch;
+  const int K = g.K, N = g.N;
+  const int tiles_n = (N + 31) >> 5;
+  const int tile = pyz_xcd_remap(blockIdx.x, gridDim.x);
+  const int i0 = (tile / tiles_n) * 32, n0 = (tile % tiles_n) * 32;
+  const int i = i0 + r, n = min(n0 + r, N - 1);
+  const int ic = min(i, K - 1);
+  const bool is_w = i < K, is_b = i == K;
+  const float *ap = g.in + ic;
+  const float *dp = g.aux + n;
+  const int32_t *idx = g.row_idx ? g.row_idx + g.ctl->row_off : nullptr;
+  const float fb = (float)batch;
+  f32x16 acc = {0}, acc2 = {0};
+  const int steps = (batch + 1) >> 1;
+  int s = (steps * w) / S;
+  const int se = (steps * (w + 1)) / S;
+  if (idx) {
+    pyz_wgrad_steps<16, true, true>(s, se, acc, ap, dp, idx, g.lda, N, batch, h, r, is_w, is_b, &acc2, fb);
+    pyz_wgrad_steps<4, true, true>(s, se, acc, ap, dp, idx, g.lda, N, batch, h, r, is_w, is_b, &acc2, fb);
+    pyz_wgrad_steps<1, true, true>(s, se, acc, ap, dp, idx, g.lda, N, batch, h, r, is_w, is_b, &acc2, fb);
+  } else {
+    pyz_wgrad_steps<16, false, true>(s, se, acc, ap, dp, idx, g.lda, N, batch, h, r, is_w, is_b, &acc2, fb);
+    pyz_wgrad_steps<4, false, true>(s, se, acc, ap, dp, idx, g.lda, N, batch, h, r, is_w, is_b, &acc2, fb);
+    pyz_wgrad_steps<1, false, true>(s, se, acc, ap, dp, idx, g.lda, N, batch, h, r, is_w, is_b, &acc2, fb);
+  }
+  float *op = g.out + g.w_off, *op2 = out2 + g.w_off;
+  pyz_tile_epilogue(acc, red, [&](int ro, int co, float v) {
+    const int ii = i0 + ro, nn = n0 + co;
+    if (ii <= K && nn < N) op[(long long)ii * N + nn] = v;
+  });
+  __syncthreads();   // every wave has read the first round of `red`
+  pyz_tile_epilogue(acc2, red, [&](int ro, int co, float v) {
+    const int ii = i0 + ro, nn = n0 + co;
+    if (ii <= K && nn < N) op2[(long long)ii * N + nn] = v / fb;
   });
 }
 
@@ -725,4 +777,10 @@ static inline void pyz_launch_bwd_weight(const DenseArgs &g, int grid_batch, int
   const long long tiles = (long long)((g.K + 1 + 31) / 32) * ((g.N + 31) / 32);
   const int S = pyz_pick_waves(tiles * P, (grid_batch + 1) / 2);
   PYZ_LAUNCH(k_dense_bwd_weight, dim3((unsigned)tiles, P), dim3(64 * S), S > 1 ? S * 4096 : 0, st, g);
+}
+
+static inline void pyz_launch_bwd_weight_sq(const DenseArgs &g, float *out2, int grid_batch, hipStream_t st) {   // one chain
+  const long long tiles = (long long)((g.K + 1 + 31) / 32) * ((g.N + 31) / 32);
+  const int S = pyz_pick_waves(tiles, (grid_batch + 1) / 2);
+  PYZ_LAUNCH(k_dense_bwd_weight_sq, dim3((unsigned)tiles), dim3(64 * S), S > 1 ? S * 4096 : 0, st, g, out2);
 }

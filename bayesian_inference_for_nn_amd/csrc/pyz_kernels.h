@@ -243,6 +243,75 @@ __global__ void k_swag_update(float *theta, float *mean, float *sq_mean, float *
   }
 }
 
+// ---------------------------------------------------------------- ADAM / VADAM
+// The scalars of one ADAM.step (ADAM.py:77-84) / VADAM.step (VADAM.py:88-96) update.  The reference's Python-float
+// expressions become float32 tensors once, so the host computes each in float64 and rounds it once: b1 = beta_1,
+// c1 = 1 - beta_1, b2 = beta_2, c2 = 1 - beta_2, bc1 = 1 - beta_1^epoch, bc2 = 1 - beta_2^epoch (with beta_2 = 1 - 2^-52,
+// b2 rounds to 1.0 but c2 and bc2 stay exact).  eps = the denominator's epsilon (1e-3, VADAM: lam / N); decay = lam / N
+// (0 for ADAM).
+struct AdamScal {
+  float lr, b1, c1, b2, c2, bc1, bc2, eps, decay;
+};
+
+struct PyzAdamOut {
+  float th, m, v;
+};
+
+// w = the weight (VADAM: the perturbed one), m0 / v0 = the moments, g = batch mean of the per-example gradients,
+// s = batch mean of their squares
+__device__ __forceinline__ PyzAdamOut pyz_adam_math(const AdamScal &a, const float w, const float m0, const float v0,
+                                                    const float g, const float s) {
+  PyzAdamOut o;
+  o.m = a.b1 * m0 + a.c1 * (g + a.decay * w);
+  o.v = a.b2 * v0 + a.c2 * s;
+  const float mh = o.m / a.bc1, vh = o.v / a.bc2;
+  o.th = w - a.lr * mh / (sqrtf(vh) + a.eps);
+  return o;
+}
+
+// ADAM / VADAM update for nets the fused path does not take: g and s come from the weight-gradient kernels
+// (k_dense_bwd_weight_sq); the first wave also finalises the batch loss.
+__global__ void k_adam_update(float *theta, float *m, float *v, const float *g, const float *s, long long D, AdamScal a,
+                              const StepCtl *ctl, const double *part, int nblk, float *loss, int *nonfinite) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < D) {
+    const PyzAdamOut o = pyz_adam_math(a, theta[e], m[e], v[e], g[e], s[e]);
+    theta[e] = o.th;
+    m[e] = o.m;
+    v[e] = o.v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) {
+    const double tot = pyz_sum_partials(part, nblk);
+    if (threadIdx.x == 0) {
+      loss[0] = (float)(tot / (double)ctl->batch);
+      pyz_note_loss(nonfinite, loss[0]);
+    }
+  }
+}
+
+// VADAM.step's weight perturbation (VADAM.py:59-65): w += eps / sqrt(N (v + lam)), eps ~ N(0, 1) from the Philox stream
+// (seed, PYZ_STREAM_VADAM, step) or injected.  Not undone after the step: the weights random-walk, as in the reference.
+// Each thread owns four consecutive elements (one Philox call).
+__global__ void k_vadam_perturb(float *theta, const float *v, long long D, float lam, float num_data, uint64_t seed,
+                                uint32_t step, const float *eps) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long e0 = 4 * t;
+  if (e0 >= D) return;
+  float z[4];
+  if (eps) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = (e0 + j < D) ? eps[e0 + j] : 0.0f;
+  } else {
+    const float4 q = pyz_normal4(seed, PYZ_STREAM_VADAM, step, (uint64_t)t);
+    z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long long e = e0 + j;
+    if (e < D) theta[e] += z[j] * (1.0f / sqrtf(num_data * (v[e] + lam)));
+  }
+}
+
 // SGLD.step (SGLD.py:64-93), fused over the flat vector:
 //   noise = lr * z;  theta += -lr * (grad + noise)
 //   mean <- (mean * n + theta) / (n + 1);  sq_mean <- (sq_mean * n + theta^2) / (n + 1)

@@ -154,6 +154,28 @@ class MLPPlan:
         check(self.lib.pyz_sgd_step(self.h, ptr(theta), ptr(x), ptr(y), ptr(row_idx), batch, float(lr), ptr(loss_out),
                                     _stream()))
 
+    def adam_step(self, theta, m, v, x, y, lr, beta_1, beta_2, epoch, loss_out, denom_eps=1e-3, decay=0.0, batch=None,
+                  row_idx=None):
+        """ADAM.step (ADAM.py:42-84); VADAM's update with decay = denom_eps = lam / N.  m / v are the moment vectors;
+        beta_1 / beta_2 go to the library as float64 (it rounds 1 - beta and 1 - beta^epoch to float32 once)."""
+        for t, nm in ((theta, "theta"), (m, "m"), (v, "v")):
+            _f32(t, (self.D,), nm)
+        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+        self._check_xy(x, y, row_idx, batch)
+        check(self.lib.pyz_adam_step(self.h, ptr(theta), ptr(m), ptr(v), ptr(x), ptr(y), ptr(row_idx), batch, float(lr),
+                                     float(beta_1), float(beta_2), int(epoch), float(denom_eps), float(decay),
+                                     ptr(loss_out), _stream()))
+
+    def vadam_perturb(self, theta, v, lam, num_data, step, seed, eps=None):
+        """VADAM.step's perturbation (VADAM.py:59-65): theta += eps / sqrt(num_data (v + lam)); eps from the device
+        Philox stream (seed, STREAM_VADAM, step) or the given (D,) tensor."""
+        _f32(theta, (self.D,), "theta")
+        _f32(v, (self.D,), "v")
+        if eps is not None:
+            _f32(eps, (self.D,), "eps")
+        check(self.lib.pyz_vadam_perturb(self.h, ptr(theta), ptr(v), float(lam), float(num_data), int(step), int(seed),
+                                         ptr(eps), _stream()))
+
     def swag_step(self, theta, mean, sq_mean, dev_row, x, y, lr, n, update_moments, loss_out, batch=None, row_idx=None):
         for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
             _f32(t, (self.D,), nm)

@@ -110,6 +110,25 @@ int pyz_swag_step(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean,
                   const float *d_x, const void *d_y, const int32_t *d_row_idx, int batch, float lr,
                   int64_t n, int update_moments, float *d_loss, void *stream);
 
+/* ---- ADAM.step (Pyesian/optimizers/ADAM.py:42-84) and the update of VADAM.step (VADAM.py:67-96), one chain.  With g
+ * the batch mean of the per-example gradients and s the batch mean of their squares (the reference's squared
+ * tape.jacobian, computed here as (A o A)^T (B Delta o B Delta) / B beside A^T Delta, with no Jacobian):
+ *   m <- beta_1 m + (1 - beta_1) (g + decay * theta);  v <- beta_2 v + (1 - beta_2) s
+ *   theta <- theta - lr * (m / (1 - beta_1^epoch)) / (sqrt(v / (1 - beta_2^epoch)) + denom_eps)
+ * ADAM: decay = 0, denom_eps = 1e-3 (ADAM.py:84); VADAM: decay = denom_eps = lam / N (VADAM.py:91,95-96), theta = the
+ * perturbed weights.  The bias correction uses the epoch count (>= 1), not the step count, as the reference does.
+ * 1 - beta, beta^epoch are evaluated in float64 and rounded to float32 once (the reference's Python-float
+ * expressions); beta_1, beta_2 in [0, 1).  d_m / d_v: float32[D]; d_loss receives the batch loss. */
+int pyz_adam_step(pyz_mlp *mlp, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                  const int32_t *d_row_idx, int batch, float lr, double beta_1, double beta_2, int64_t epoch,
+                  float denom_eps, float decay, float *d_loss, void *stream);
+
+/* ---- VADAM.step's weight perturbation (VADAM.py:59-65): theta += eps / sqrt(num_data (v + lam)), eps ~ N(0,1) from
+ * the library's Philox stream (seed, stream 5, step) or from d_eps (float32[D]) when given.  The perturbation is not
+ * undone after the step (the reference's weights random-walk). */
+int pyz_vadam_perturb(pyz_mlp *mlp, float *d_theta, const float *d_v, float lam, float num_data, int64_t step,
+                      uint64_t seed, const float *d_eps, void *stream);
+
 /* ---- L2/L3: SGLD.step (SGLD.py:54-95).  noise = lr * z, z ~ N(0,1) from the
  * library's Philox stream (seed, step n) or from d_unit_noise (float32[D]) when
  * given; theta += -lr * (grad + noise); mean/sq_mean running moments with
