@@ -20,6 +20,8 @@ from oracle import sgld as o_sgld
 from oracle import svgd as o_svgd
 from oracle import swag as o_swag
 
+from head_cases import close_blocks
+
 
 def close(gpu, ref, rel=1e-4, what=""):
     gpu = np.asarray(gpu.detach().cpu().numpy() if hasattr(gpu, "detach") else gpu, dtype=np.float64)
@@ -106,7 +108,7 @@ def test_loss_grad_and_forward(eng, name):
     loss, grad = plan.loss_grad(dev(theta), dev(x), ydev(spec, y))
     rl, rg, rout = o_mlp.loss_and_grad(theta, x, y, spec)
     close(loss, [rl], what="loss")
-    close(grad[0], rg, what="grad")
+    close_blocks(grad[0], rg, spec, what="grad")   # every layer's W and b on its own scale
     out = plan.forward(dev(theta), dev(x))
     close(out[0], rout, what="forward")
     if spec.loss == "scce":   # integer class labels bit-exact
