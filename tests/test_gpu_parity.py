@@ -154,7 +154,7 @@ def test_wide_layers_many_particles(eng, monkeypatch, lds):
     for p in (0, 1, 17, 63):
         rl, rg, _ = o_mlp.loss_and_grad(thetas[p], x[idx], y[idx], spec)
         close(loss[p:p + 1], [rl], what=f"loss[{p}]")
-        close(grad[p], rg, what=f"grad[{p}]")
+        close_blocks(grad[p], rg, spec, what=f"grad[{p}]")
     plan.close()
 
 
@@ -194,7 +194,7 @@ def test_full_size_mnist_gradient(eng):
         loss, grad = plan.loss_grad(dev(theta), dev(x), dev(y, torch.int32), batch=b, row_idx=dev(idx, torch.int32))
         rl, rg, _ = o_mlp.loss_and_grad(theta, x[idx], y[idx], spec)
         close(loss, [rl], what="loss")
-        close(grad[0], rg, what="grad")
+        close_blocks(grad[0], rg, spec, what="grad")
     plan.close()
 
 
