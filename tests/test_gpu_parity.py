@@ -402,7 +402,10 @@ def test_list_valued_priors_bbb_and_hmc(eng, monkeypatch):
 def test_hmc_step_matches_oracle(eng, name, L, fused, multi, monkeypatch):
     """fused = 1: small 2-layer models run inside workgroups that keep the chain state in LDS -- one per
     chain (pyz_hmc_fused.h), or, with multi = 1 and at least 192 rows, NW row slices per chain and one
-    launch per gradient evaluation (pyz_hmc_multi.h); fused = 0 forces the generic multi-launch path."""
+    launch per gradient evaluation (pyz_hmc_multi.h); fused = 0 forces the generic multi-launch path.
+    A first check at a few shapes; the 1e-4 on q below cannot see a wrong gradient (most of the move is L eps z).
+    tests/test_gpu_hmc_matrix.py asserts which kernel ran, covers every instantiation and compares the gradient
+    part of the move."""
     monkeypatch.setenv("PYZ_HMC_FUSED", str(fused))
     monkeypatch.setenv("PYZ_HMC_MULTI", str(multi))
     spec, n = SPECS[name]
