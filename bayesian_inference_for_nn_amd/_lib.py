@@ -13,7 +13,7 @@ LOSS = {"scce": 0, "mse": 1}
 SWEEP = {"gauss_seidel": 0, "jacobi": 1}
 GAMMA_MEDIAN = -1.0       # PYZ_SVGD_GAMMA_MEDIAN
 
-STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM = 0, 1, 2, 3, 4, 5
+STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM, STREAM_BSAM = 0, 1, 2, 3, 4, 5, 6
 
 
 class PyzError(RuntimeError):
@@ -40,6 +40,8 @@ SIGNATURES = {
     "pyz_swag_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, C.c_int, _f, _i64, C.c_int, _p, _p]),
     "pyz_adam_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int, _f, C.c_double, C.c_double, _i64, _f, _f, _p, _p]),
     "pyz_vadam_perturb": (C.c_int, [_p, _p, _p, _f, _f, _i64, _u64, _p, _p]),
+    "pyz_bsam_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int, _f, C.c_double, C.c_double, _f, _f, _f, _f, _i64, _u64,
+                              _p, _p, _p]),
     "pyz_sgld_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int, _f, _i64, _u64, _p, _p, _p]),
     "pyz_sgld_run": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _i64, _i64, _u64,
                                _p, C.c_int, _p]),

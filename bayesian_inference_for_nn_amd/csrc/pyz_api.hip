@@ -443,6 +443,26 @@ void launch_wgrad_adam(pyz_mlp *m, const float *x, const int32_t *row_idx, int g
   }
 }
 
+// BSAM (one chain): every layer's gradient and the ascent (phase 0) or the update (phase 1) in one launch
+void launch_wgrad_bsam(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl, int phase,
+                       BsamArgs &a, hipStream_t st, const float *gathered) {
+  const int tiles = wgrad_layers(m, 1, x, row_idx, ctl, a.w, gathered);
+  const int S = pyz_pick_waves(tiles, (grid_batch + 1) / 2);
+  const dim3 grid(tiles + 1);   // + the duties workgroup
+#define PYZ_BSAM_CASE(W, LDS)                                                           \
+  if (phase == 0) PYZ_LAUNCH((k_wgrad_bsam<W, 0>), grid, dim3(64 * W), LDS, st, a);     \
+  else PYZ_LAUNCH((k_wgrad_bsam<W, 1>), grid, dim3(64 * W), LDS, st, a);                \
+  break
+  switch (S) {
+    case 1: PYZ_BSAM_CASE(1, 0);
+    case 2: PYZ_BSAM_CASE(2, 2 * 4096);
+    case 4: PYZ_BSAM_CASE(4, 4 * 4096);
+    case 8: PYZ_BSAM_CASE(8, 8 * 4096);
+    default: PYZ_BSAM_CASE(16, 16 * 4096);
+  }
+#undef PYZ_BSAM_CASE
+}
+
 inline float *batch_buf(pyz_mlp *m, int slot) { return m->xb + (size_t)slot * m->max_batch * m->dims[0]; }
 
 // chained runs whose batches are assembled one step ahead (PrepArgs, pyz_fused.h): single chain, fused path, a hidden layer
@@ -531,6 +551,18 @@ void launch_loss_backward(pyz_mlp *m, const float *theta, long long theta_ps, in
   launch_loss(m, P, y, row_idx, grid_batch, ctl, want_grad, st);
   m->cur_nblk = loss_nblk(m, grid_batch);
   if (want_grad) launch_backward(m, theta, theta_ps, P, x, row_idx, grid_batch, ctl, upd.grad, st, adam ? m->grad2 : nullptr);
+}
+
+// one gradient pass of a BSAM step on the fused path (launch_loss_backward's eager sequence): forward, head, data
+// gradients of the hidden layers, then k_wgrad_bsam<phase> with its epilogue
+void launch_bsam_pass(pyz_mlp *m, const float *theta, const float *x, const void *y, const int32_t *row_idx, int grid_batch,
+                      int phase, BsamArgs &a, hipStream_t st) {
+  static const int use_xb = pyz_env_int("PYZ_GATHER_COPY", 1);  // 1: forward leaves a contiguous batch copy
+  float *xb = (use_xb && row_idx && m->L > 1) ? m->xb : nullptr;
+  launch_forward(m, theta, m->D, 1, x, row_idx, grid_batch, m->ctl, st, xb, m->L - 1);   // hidden layers
+  launch_head(m, theta, m->D, 1, x, y, row_idx, grid_batch, m->ctl, true, st);
+  launch_bwd_data_hidden(m, theta, m->D, 1, grid_batch, m->ctl, st);
+  launch_wgrad_bsam(m, x, row_idx, grid_batch, m->ctl, phase, a, st, xb);
 }
 
 int check_loss_combo(const pyz_mlp *m) {
@@ -805,6 +837,60 @@ int pyz_vadam_perturb(pyz_mlp *m, float *d_theta, const float *d_v, float lam, f
   if (step < 0) return pyz_fail(PYZ_E_INVALID, "negative step");
   PYZ_LAUNCH(k_vadam_perturb, dim3(cdiv(cdiv(m->D, 4), 256)), dim3(256), 0, as_stream(stream), d_theta, d_v, m->D, lam,
              num_data, seed, (uint32_t)step, d_eps);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- BSAM (BSAM.py:46-119)
+int pyz_bsam_step(pyz_mlp *m, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                  const int32_t *d_row_idx, int batch, float lr, double beta_1, double beta_2, float lam, float rho,
+                  float gam, float num_data, int64_t step, uint64_t seed, const float *d_eps, float *d_loss, void *stream) {
+  int rc = check_call(m, 1, batch);
+  if (rc) return rc;
+  if ((rc = check_loss_combo(m))) return rc;
+  if (!d_theta || !d_m || !d_v || !d_x || !d_y || !d_loss) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (!(beta_1 >= 0.0 && beta_1 < 1.0) || !(beta_2 >= 0.0 && beta_2 < 1.0))
+    return pyz_fail(PYZ_E_INVALID, "beta_1 = %g, beta_2 = %g: both must lie in [0, 1)", beta_1, beta_2);
+  if (!(num_data > 0.0f)) return pyz_fail(PYZ_E_INVALID, "num_data = %g must be positive", (double)num_data);
+  if (step < 0) return pyz_fail(PYZ_E_INVALID, "negative step");
+  const bool fused = can_fuse(m);
+  if ((rc = need_grad2(m, 1)) || (!fused && (rc = need_grad(m, 1)))) return rc;   // grad2 keeps the first pass's gradient
+  hipStream_t st = as_stream(stream);
+  BsamArgs a{};
+  a.w.mode = PYZ_UPD_NONE;
+  a.m = d_m;
+  a.v = d_v;
+  a.g1 = m->grad2;
+  // each scalar in float64, rounded to float32 once (see BsamScal)
+  a.a.lr = lr;
+  a.a.b1 = (float)beta_1;
+  a.a.c1 = (float)(1.0 - beta_1);
+  a.a.b2 = (float)beta_2;
+  a.a.c2 = (float)(1.0 - beta_2);
+  a.a.lam = lam;
+  a.a.rho = rho;
+  a.a.gam = gam;
+  a.a.inv_n = (float)(1.0 / (double)num_data);
+  PYZ_LAUNCH(k_bsam_perturb, dim3(cdiv(cdiv(m->D, 4), 256)), dim3(256), 0, st, d_theta, d_v, m->D, a.a.inv_n, seed,
+             (uint32_t)step, d_eps);
+  set_ctl_lazy(m, batch, lr, 0);   // (carried by the first pass's first kernel; the second pass finds it in place)
+  if (fused) {  // each pass ends in its weight-gradient launch: gradients + ascent, gradients + update
+    a.w.theta = d_theta;
+    a.w.loss = d_loss;
+    launch_bsam_pass(m, d_theta, d_x, d_y, d_row_idx, batch, 0, a, st);
+    a.w.loss = d_loss + 1;
+    launch_bsam_pass(m, d_theta, d_x, d_y, d_row_idx, batch, 1, a, st);
+  } else {
+    a.w.grad = m->grad;
+    a.w.grad_pstride = m->D;
+    const dim3 grid(cdiv(m->D, 256)), block(256);
+    launch_loss_backward(m, d_theta, m->D, 1, d_x, d_y, d_row_idx, batch, m->ctl, true, a.w, st);
+    PYZ_LAUNCH(k_bsam_ascent, grid, block, 0, st, d_theta, d_v, m->grad, m->grad2, m->D, a.a, m->ctl, m->part, m->cur_nblk,
+               d_loss, m->nonfinite);
+    launch_loss_backward(m, d_theta, m->D, 1, d_x, d_y, d_row_idx, batch, m->ctl, true, a.w, st);
+    PYZ_LAUNCH(k_bsam_update, grid, block, 0, st, d_theta, d_m, d_v, m->grad, m->grad2, m->D, a.a, m->ctl, m->part,
+               m->cur_nblk, d_loss + 1, m->nonfinite);
+  }
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
 }

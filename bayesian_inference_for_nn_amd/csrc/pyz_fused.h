@@ -1185,3 +1185,134 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_adam(AdamArgs A) {
     pyz_st(A.v + ee[q], o.v, g.wt);
   }
 }
+
+// ---------------------------------------------------------------- BSAM: gradients + ascent, gradients + update
+// BSAM.step (BSAM.py:46-119) takes two gradient passes on one batch.  After the first the weights ascend along g1 / v
+// and g1 is kept; after the second m, v and the weights are updated from g2 and the kept g1 (pyz_bsam_ascent_math /
+// pyz_bsam_math, pyz_kernels.h).  Both are elementwise in the gradient tile a workgroup of k_wgrad_all has just reduced,
+// so each pass ends in the epilogue of its weight-gradient launch: k_wgrad_all's tile walk, one MFMA chain, the
+// reduction across the S waves through LDS and the duties workgroup (loss, non-finite count), with
+//   PHASE 0: reads w, v;         writes g1 (the tile's gradient) and w <- w + rho g1 / v
+//   PHASE 1: reads w, m, v, g1;  writes m, v and w
+// No launch reads the weights after the head and the data-gradient kernels of its pass, so they are updated in place.
+// A kernel of its own (not a mode of k_wgrad_all or k_wgrad_adam): their instantiations are left as they were.
+struct BsamArgs {
+  WgradArgs w;   // layers, tiles, theta, the duties (loss, nonfinite); mode PYZ_UPD_NONE, grad unused
+  float *m, *v, *g1;
+  BsamScal a;
+};
+
+template <int S, int PHASE>
+__global__ void __launch_bounds__(64 * S) k_wgrad_bsam(BsamArgs A) {
+  extern __shared__ float red[];
+  const WgradArgs &g = A.w;
+  constexpr int EPT = 16 / S;  // tile elements per thread in the epilogue
+  const int w = pyz_wave_id(), l = threadIdx.x & 63;
+  const int r = l & 31, h = l >> 5;
+  if (blockIdx.x >= (unsigned)g.tiles) {  // the duties workgroup: the pass's loss and the non-finite count
+    if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    return;
+  }
+  const int tile = pyz_xcd_remap(blockIdx.x, g.tiles);
+  int li = 0;
+  while (li + 1 < g.L && tile >= g.lay[li + 1].tile0) ++li;
+  const WgradLayer &ly = g.lay[li];
+  const int batch = g.ctl->batch;
+  const int K = ly.K, N = ly.N;
+  const int tiles_n = (N + 31) >> 5;
+  const int t = tile - ly.tile0;
+  const int i0 = (t / tiles_n) * 32, n0 = (t % tiles_n) * 32;
+  const long long w_off = ly.w_off;
+
+  // the state of this thread's elements, fetched behind the first group of operand loads (see k_wgrad_all)
+  long long ee[EPT];
+  bool ev[EPT];
+  float th0[EPT], v0[EPT], m0[PHASE ? EPT : 1], g10[PHASE ? EPT : 1];
+  auto prefetch = [&]() {
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      int ro, co;
+      if (S == 1) {
+        ro = (q & 3) + 8 * (q >> 2) + 4 * h;
+        co = r;
+      } else {
+        const int e = threadIdx.x + q * 64 * S;
+        ro = e >> 5;
+        co = e & 31;
+      }
+      const int ii = i0 + ro, nn = n0 + co;
+      ev[q] = ii <= K && nn < N;
+      ee[q] = w_off + (long long)min(ii, K) * N + min(nn, N - 1);
+      th0[q] = g.theta[ee[q]];
+      v0[q] = A.v[ee[q]];
+      if constexpr (PHASE == 1) {
+        m0[q] = A.m[ee[q]];
+        g10[q] = A.g1[ee[q]];
+      }
+    }
+  };
+
+  const int i = i0 + r, n = min(n0 + r, N - 1);
+  const int ic = min(i, K - 1);
+  const bool is_w = i < K, is_b = i == K;
+  const float *ap = ly.in + ic;
+  const float *dp = ly.delta + n;
+  const int32_t *idx = (ly.gather && g.row_idx) ? g.row_idx + g.ctl->row_off : nullptr;
+  f32x16 acc = {0};
+  const int steps = (batch + 1) >> 1;
+  int s = (steps * w) / S;
+  const int se = (steps * (w + 1)) / S;
+  if (idx) {
+    prefetch();
+    for (int s0 = s; s0 < se; s0 += 32) {   // gathered rows: k_wgrad_all's index broadcast
+      const int idxv = idx[min(2 * s0 + l, batch - 1)];
+      const int lda = ly.lda;
+      pyz_steps1_all(
+          s0, min(s0 + 32, se), acc,
+          [&](int st, float &a, float &d) {
+            const int bc = PYZ_HOT(min(2 * st + h, batch - 1), batch);
+            const long long row = PYZ_HOT(__shfl(idxv, 2 * (st - s0) + h, 64), batch);
+            a = ap[row * lda];
+            d = dp[(long long)bc * N];
+          },
+          [&](int st, float &a, float &d) {
+            const bool vb = 2 * st + h < batch;
+            a = vb ? (is_w ? a : (is_b ? 1.0f : 0.0f)) : 0.0f;
+            d = vb ? d : 0.0f;
+          });
+    }
+  } else {
+    pyz_wgrad_accumulate(acc, ly.in, ic, ly.delta, n, ly.lda, N, batch, s, se, h, is_w, is_b, prefetch);
+  }
+  float gv[EPT];
+  if (S == 1) {
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) gv[q] = acc[q];
+  } else {
+    float *my = red + w * 1024;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) my[((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + r] = acc[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < EPT; ++q) {
+      const int e = threadIdx.x + q * 64 * S;
+      float v = red[e];
+#pragma unroll
+      for (int ww = 1; ww < S; ++ww) v += red[ww * 1024 + e];
+      gv[q] = v;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < EPT; ++q) {
+    if (!ev[q]) continue;
+    if constexpr (PHASE == 0) {
+      pyz_st(A.g1 + ee[q], gv[q], g.wt);
+      pyz_st(g.theta + ee[q], pyz_bsam_ascent_math(A.a, th0[q], v0[q], gv[q]), g.wt);
+    } else {
+      const PyzBsamOut o = pyz_bsam_math(A.a, th0[q], m0[q], v0[q], gv[q], g10[q]);
+      pyz_st(g.theta + ee[q], o.th, g.wt);
+      pyz_st(A.m + ee[q], o.m, g.wt);
+      pyz_st(A.v + ee[q], o.v, g.wt);
+    }
+  }
+}

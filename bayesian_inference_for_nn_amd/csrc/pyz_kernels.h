@@ -312,6 +312,98 @@ __global__ void k_vadam_perturb(float *theta, const float *v, long long D, float
   }
 }
 
+// ---------------------------------------------------------------- BSAM
+// The scalars of one BSAM.step (BSAM.py:46-119).  As for AdamScal the host computes each Python-float expression in
+// float64 and rounds it once: b1 = beta_1, c1 = 1 - beta_1, b2 = beta_2, c2 = 1 - beta_2 (the reference driver's
+// beta_2 = 0.9999999 leaves c2 = 1e-7, which a float32 subtraction would turn into 1.19e-7), inv_n = 1 / N.
+struct BsamScal {
+  float lr, b1, c1, b2, c2, lam, rho, gam, inv_n;
+};
+
+struct PyzBsamOut {
+  float th, m, v;
+};
+
+// BSAM.py:63-68: w += eps * (1 / (N v))
+__device__ __forceinline__ float pyz_bsam_perturb_math(const float inv_n, const float w, const float v, const float eps) {
+  return w + eps * (inv_n / v);
+}
+
+// BSAM.py:85-91, the ascent after the first pass: w += rho * (g1 / v)
+__device__ __forceinline__ float pyz_bsam_ascent_math(const BsamScal &a, const float w, const float v, const float g1) {
+  return w + a.rho * (g1 / v);
+}
+
+// BSAM.py:110-117, the update after the second pass.  w = the ascended weight, g2 = the second pass's gradient, g1 = the
+// first pass's.  As written: the square root is taken of the v already scaled by beta_2, lam and gam are added to g1
+// as scalars, and the step divides by v itself (no bias correction, no square root).
+__device__ __forceinline__ PyzBsamOut pyz_bsam_math(const BsamScal &a, const float w, const float m0, const float v0,
+                                                    const float g2, const float g1) {
+  PyzBsamOut o;
+  o.m = a.b1 * m0 + a.c1 * (g2 + a.lam * w);
+  const float vb = a.b2 * v0;
+  o.v = vb + a.c2 * (sqrtf(vb) * fabsf(g1 + a.lam + a.gam));
+  o.th = w - a.lr * o.m / o.v;
+  return o;
+}
+
+// the batch loss of a pass from the head's / loss kernel's partials (first wave of workgroup 0 of the elementwise kernels)
+__device__ __forceinline__ void pyz_bsam_loss(const StepCtl *ctl, const double *part, int nblk, float *loss, int *nonfinite) {
+  const double tot = pyz_sum_partials(part, nblk);
+  if (threadIdx.x == 0) {
+    loss[0] = (float)(tot / (double)ctl->batch);
+    pyz_note_loss(nonfinite, loss[0]);
+  }
+}
+
+// BSAM.step's weight perturbation: eps ~ N(0, 1) from the Philox stream (seed, PYZ_STREAM_BSAM, step) or injected.  Not
+// undone after the step, as in the reference.  Each thread owns four consecutive elements (one Philox call).
+__global__ void k_bsam_perturb(float *theta, const float *v, long long D, float inv_n, uint64_t seed, uint32_t step,
+                               const float *eps) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long e0 = 4 * t;
+  if (e0 >= D) return;
+  float z[4];
+  if (eps) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = (e0 + j < D) ? eps[e0 + j] : 0.0f;
+  } else {
+    const float4 q = pyz_normal4(seed, PYZ_STREAM_BSAM, step, (uint64_t)t);
+    z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long long e = e0 + j;
+    if (e < D) theta[e] = pyz_bsam_perturb_math(inv_n, theta[e], v[e], z[j]);
+  }
+}
+
+// BSAM for nets the fused path does not take, after the first pass: g (from the weight-gradient kernels) is kept in g1
+// and the weights ascend; the first wave also finalises the first pass's loss.
+__global__ void k_bsam_ascent(float *theta, const float *v, const float *g, float *g1, long long D, BsamScal a,
+                              const StepCtl *ctl, const double *part, int nblk, float *loss, int *nonfinite) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < D) {
+    const float gv = g[e];
+    g1[e] = gv;
+    theta[e] = pyz_bsam_ascent_math(a, theta[e], v[e], gv);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) pyz_bsam_loss(ctl, part, nblk, loss, nonfinite);
+}
+
+// ... and after the second pass: the update from g2 = g and the kept g1; the first wave finalises the second loss.
+__global__ void k_bsam_update(float *theta, float *m, float *v, const float *g, const float *g1, long long D, BsamScal a,
+                              const StepCtl *ctl, const double *part, int nblk, float *loss, int *nonfinite) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < D) {
+    const PyzBsamOut o = pyz_bsam_math(a, theta[e], m[e], v[e], g[e], g1[e]);
+    theta[e] = o.th;
+    m[e] = o.m;
+    v[e] = o.v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 64) pyz_bsam_loss(ctl, part, nblk, loss, nonfinite);
+}
+
 // SGLD.step (SGLD.py:64-93), fused over the flat vector:
 //   noise = lr * z;  theta += -lr * (grad + noise)
 //   mean <- (mean * n + theta) / (n + 1);  sq_mean <- (sq_mean * n + theta^2) / (n + 1)

@@ -18,6 +18,7 @@
 #define PYZ_STREAM_INIT 3u
 #define PYZ_STREAM_PREDICT 4u
 #define PYZ_STREAM_VADAM 5u  // VADAM weight perturbation (VADAM.py:59-65), step = the optimizer step
+#define PYZ_STREAM_BSAM 6u   // BSAM weight perturbation (BSAM.py:63-68), step = the optimizer step
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;

@@ -176,6 +176,22 @@ class MLPPlan:
         check(self.lib.pyz_vadam_perturb(self.h, ptr(theta), ptr(v), float(lam), float(num_data), int(step), int(seed),
                                          ptr(eps), _stream()))
 
+    def bsam_step(self, theta, m, v, x, y, lr, beta_1, beta_2, lam, rho, gam, num_data, step, seed, loss_out, eps=None,
+                  batch=None, row_idx=None):
+        """BSAM.step (BSAM.py:46-119): perturbation (Philox stream (seed, STREAM_BSAM, step), or the given (D,) eps),
+        first pass + ascent, second pass + update of m, v and theta.  loss_out: (2,) float32, receives l1 and l2;
+        beta_1 / beta_2 go to the library as float64 (it rounds 1 - beta and 1 / num_data to float32 once)."""
+        for t, nm in ((theta, "theta"), (m, "m"), (v, "v")):
+            _f32(t, (self.D,), nm)
+        _f32(loss_out, (2,), "loss_out")
+        if eps is not None:
+            _f32(eps, (self.D,), "eps")
+        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+        self._check_xy(x, y, row_idx, batch)
+        check(self.lib.pyz_bsam_step(self.h, ptr(theta), ptr(m), ptr(v), ptr(x), ptr(y), ptr(row_idx), batch, float(lr),
+                                     float(beta_1), float(beta_2), float(lam), float(rho), float(gam), float(num_data),
+                                     int(step), int(seed), ptr(eps), ptr(loss_out), _stream()))
+
     def swag_step(self, theta, mean, sq_mean, dev_row, x, y, lr, n, update_moments, loss_out, batch=None, row_idx=None):
         for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
             _f32(t, (self.D,), nm)

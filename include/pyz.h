@@ -129,6 +129,25 @@ int pyz_adam_step(pyz_mlp *mlp, float *d_theta, float *d_m, float *d_v, const fl
 int pyz_vadam_perturb(pyz_mlp *mlp, float *d_theta, const float *d_v, float lam, float num_data, int64_t step,
                       uint64_t seed, const float *d_eps, void *stream);
 
+/* ---- BSAM.step (Pyesian/optimizers/BSAM.py:46-119), one chain, both gradient passes of the step on one batch:
+ *   perturb (:63-68)      theta += eps * (1 / (N v)), eps ~ N(0,1) from the library's Philox stream (seed, stream 6,
+ *                         step) or from d_eps (float32[D]) when given; never undone
+ *   first pass (:70-92)   l1, g1 = batch-mean loss and its gradient at the perturbed theta; theta += rho * (g1 / v),
+ *                         never undone either; g1 is kept
+ *   second pass (:94-117) l2, g2 at the ascended theta, then per element, in this order:
+ *       m <- beta_1 m + (1 - beta_1) (g2 + lam * theta);  v <- beta_2 v;
+ *       v <- v + (1 - beta_2) (sqrt(v) * |g1 + lam + gam|);  theta <- theta - lr * m / v
+ * The square root is taken of the v already scaled by beta_2, the gradient in the v update is the FIRST pass's, lam
+ * and gam are added to it as scalars, and the step has neither bias correction nor a square root in its denominator
+ * (all as the reference is written).  1 - beta and 1 / N (N = num_data > 0) are evaluated in float64 and rounded to
+ * float32 once; beta_1, beta_2 in [0, 1); step >= 0.  d_m / d_v: float32[D] (the reference starts from m = 0, v = 1,
+ * :121-141); d_loss: float[2] receives l1, l2.  The ascent and the update run in the epilogues of the two
+ * weight-gradient launches when the last layer has at most 32 units, else in two elementwise kernels. */
+int pyz_bsam_step(pyz_mlp *mlp, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                  const int32_t *d_row_idx, int batch, float lr, double beta_1, double beta_2, float lam, float rho,
+                  float gam, float num_data, int64_t step, uint64_t seed, const float *d_eps, float *d_loss,
+                  void *stream);
+
 /* ---- L2/L3: SGLD.step (SGLD.py:54-95).  noise = lr * z, z ~ N(0,1) from the
  * library's Philox stream (seed, step n) or from d_unit_noise (float32[D]) when
  * given; theta += -lr * (grad + noise); mean/sq_mean running moments with
