@@ -57,6 +57,9 @@ SIGNATURES = {
                               _i64, _u64, _p, _p, _p, _p, C.c_int, _p, C.c_int, _p]),
     "pyz_hmc_step": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, C.c_int, _f, _f, _f, _f, _p, _p, C.c_int, C.POINTER(_f),
                                _i64, _u64, _p, _p, _p]),
+    "pyz_hmc_run": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, C.c_int, _f, _f, _f, _f, _p, _p, C.POINTER(_f), C.c_int, C.c_int,
+                              _i64, _i64, _u64, _p, _p, _p, _p, C.c_int, _p, C.c_int, _p]),
+    "pyz_hmc_run_info": (C.c_int, [_p, C.POINTER(_i32)]),
     "pyz_svgd_step": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, C.c_int, _f, _f, _i64,
                                 C.c_int, _p, _p]),
     "pyz_svgd_gradients": (C.c_int, [_p, _p, C.c_int, _p, _p, _p, C.c_int, _p]),

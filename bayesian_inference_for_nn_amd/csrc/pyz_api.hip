@@ -56,6 +56,22 @@ struct Extra {  // lazily sized buffers kept beside the plan
   size_t up_slot_bytes = 0;
   hipEvent_t up_ev[UP_SLOTS] = {};
   unsigned long long up_count = 0;
+  // pyz_hmc_run: the proposals of a run take their uniforms and HmcCall from the device (k_hmc_feed), not from the ring
+  bool hm_fed = false;           // set around the run's calls of pyz_hmc_step: no upload, no graph of its own
+  int hm_path = 0;               // what the last pyz_hmc_step launched: 0 generic, 1 one workgroup, 2 sliced, 3 resident
+  unsigned long long hm_sig = 0; // ... and, for the sliced forms, everything its launches bake in
+  void *hr_buf = nullptr;        // HmcRunCtl, the count snapshot and the (max_p, 8) statistics of the proposal in flight
+  float *hr_tab = nullptr;       // the uniform table of the call
+  size_t hr_tab_cap = 0;         // floats
+  unsigned char *hr_host = nullptr;  // ... goes up through two pinned buffers used in turn (as tab_host does)
+  size_t hr_host_cap = 0;        // bytes per buffer
+  hipEvent_t hr_ev[2] = {};
+  unsigned long long hr_count = 0;
+  hipGraph_t hr_graph[PYZ_GRAPH_CHUNKS] = {};   // slot 0 = a chunk of proposals, the others = remainders by exact length (LRU)
+  hipGraphExec_t hr_exec[PYZ_GRAPH_CHUNKS] = {};
+  int hr_len[PYZ_GRAPH_CHUNKS] = {};
+  unsigned long long hr_use[PYZ_GRAPH_CHUNKS] = {}, hr_clock = 0, hr_key = 0;
+  int hr_captures = 0;           // graphs the last pyz_hmc_run captured
 };
 
 }  // namespace
@@ -68,6 +84,16 @@ struct pyz_mlp_full : pyz_mlp {
 namespace {
 
 inline pyz_mlp_full *full(pyz_mlp *m) { return static_cast<pyz_mlp_full *>(m); }
+
+void drop_hmc_run_graphs(Extra &x) {
+  for (int c = 0; c < PYZ_GRAPH_CHUNKS; ++c) {
+    if (x.hr_exec[c]) (void)hipGraphExecDestroy(x.hr_exec[c]);
+    if (x.hr_graph[c]) (void)hipGraphDestroy(x.hr_graph[c]);
+    x.hr_exec[c] = nullptr;
+    x.hr_graph[c] = nullptr;
+    x.hr_len[c] = 0;
+  }
+}
 
 void drop_graphs(pyz_mlp *m) {
   for (int c = 0; c < PYZ_GRAPH_CHUNKS; ++c) {
@@ -707,11 +733,12 @@ int pyz_mlp_destroy(pyz_mlp *mm) {
   drop_graphs(m);
   if (m->x.hm_exec) (void)hipGraphExecDestroy(m->x.hm_exec);
   if (m->x.hm_graph) (void)hipGraphDestroy(m->x.hm_graph);
+  drop_hmc_run_graphs(m->x);
   for (int l = 0; l < PYZ_MAX_LAYERS; ++l) {
     if (m->act[l]) (void)hipFree(m->act[l]);
     if (m->delta[l]) (void)hipFree(m->delta[l]);
   }
-  void *ptrs[] = {m->grad, m->grad2, m->qsave, m->part, m->x.part2, m->scal, m->ctl, m->tab_bs, m->xb, m->x.hm_buf, m->x.hm_res_buf, m->x.gs_res_buf, m->x.fwd_part, m->nonfinite};
+  void *ptrs[] = {m->grad, m->grad2, m->qsave, m->part, m->x.part2, m->scal, m->ctl, m->tab_bs, m->xb, m->x.hm_buf, m->x.hm_res_buf, m->x.gs_res_buf, m->x.fwd_part, m->nonfinite, m->x.hr_buf, m->x.hr_tab};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (m->x.tab_host) {
@@ -721,6 +748,10 @@ int pyz_mlp_destroy(pyz_mlp *mm) {
   if (m->x.up_host) {
     (void)hipHostFree(m->x.up_host);
     for (auto &e : m->x.up_ev) (void)hipEventDestroy(e);
+  }
+  if (m->x.hr_host) {
+    (void)hipHostFree(m->x.hr_host);
+    for (auto &e : m->x.hr_ev) (void)hipEventDestroy(e);
   }
   if (m->h_pinned) (void)hipHostFree(m->h_pinned);
   delete m;
@@ -1418,7 +1449,8 @@ int pyz_hmc_step(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_
   float *energies = m->scal + m->max_p;  // [P*8]
   float *unif = m->scal + 9 * m->max_p;  // [max_p] uniforms, then one HmcCall
   HmcCall *call_dev = reinterpret_cast<HmcCall *>(m->scal + 10 * m->max_p);  // float index 10 max_p is even
-  {
+  f->x.hm_path = 0;
+  if (!f->x.hm_fed) {   // (inside pyz_hmc_run k_hmc_feed has filled the slot)
     const size_t up_bytes = sizeof(float) * (size_t)m->max_p + sizeof(HmcCall);
     Extra &x = f->x;
     if (!x.up_host) {
@@ -1558,7 +1590,9 @@ int pyz_hmc_step(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_
         unsigned fbits[4];
         memcpy(&fbits[0], &epsilon, 4); memcpy(&fbits[1], &mass, 4); memcpy(&fbits[2], &prior_mean, 4); memcpy(&fbits[3], &prior_sigma, 4);
         for (unsigned b : fbits) mix(b);
-        const int use_graph = pyz_env_int("PYZ_HMC_GRAPH", 1);   // (read per call: tests flip it)
+        const int use_graph = fm->x.hm_fed ? 0 : pyz_env_int("PYZ_HMC_GRAPH", 1);   // (read per call: tests flip it; a run captures graphs of its own)
+        fm->x.hm_path = resident ? 3 : 2;
+        fm->x.hm_sig = key;
         auto launch_all = [&]() {
           if (resident) {
             PYZ_LAUNCH(kres, dim3(NW, P), dim3(PYZ_HM_THREADS), mlds, st, mm);
@@ -1592,6 +1626,7 @@ int pyz_hmc_step(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_
       if (lds > 64 * 1024)
         PYZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       PYZ_LAUNCH(kern, dim3(P), dim3(PYZ_HF_THREADS), lds, st, f);
+      full(m)->x.hm_path = 1;
       PYZ_LAUNCH_CHECK();
       return PYZ_OK;
     }
@@ -1657,6 +1692,196 @@ int pyz_hmc_step(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_
   PYZ_LAUNCH(k_hmc_accept, dim3(cdiv(P, 64)), dim3(64), 0, st, energies, unif, burning, d_stats, P);
   PYZ_LAUNCH(k_hmc_restore, dim3(nblk1, P), dim3(256), 0, st, d_q, m->qsave, d_stats, m->D);
   PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// The quiet HMC.train (HMC.py:106-125 around HMC.py:74-104) as one device-resident run: n_steps proposals of
+// pyz_hmc_step, each between k_hmc_feed (its uniforms and HmcCall out of the run's table) and k_hmc_record (its
+// statistics to their slot, the sample record), with no host work in between.  The proposal itself is launched by
+// pyz_hmc_step's own dispatch (Extra::hm_fed: no upload, no graph of its own).  The sliced forms (k_hmc_multi,
+// k_hmc_resident) read their scalars from the device: their proposals are captured, feed and record included, into
+// graphs of PYZ_HMC_RUN_CHUNK proposals and one of the exact remaining length, kept as sgld_run_impl keeps its graphs.
+// k_hmc_fused and the generic sequence take the step and the burning flag as kernel arguments: they are launched
+// eagerly from the loop below (the host knows both; the uniforms still come from the device), without a
+// synchronisation.  The first proposal of a call is always eager: it sizes the buffers the dispatch grows lazily
+// (nothing is allocated or cleared inside a capture) and tells which form the shape takes.
+// Extra::hm_fed is state of the plan: like every entry point that uses the plan's workspace, a plan is driven by one host
+// thread at a time (include/pyz.h), and pyz_hmc_step is not called on it from elsewhere while this function runs.
+int pyz_hmc_run(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_y, int n_rows, int L, float epsilon,
+                float mass, float prior_mean, float prior_sigma, const float *d_prior_mean_vec,
+                const float *d_prior_sigma_vec, const float *h_uniform, int n_steps, int n_burn, int64_t step0,
+                int64_t slot0, uint64_t seed, float *d_stats_all, float *d_samples, int32_t *d_freq, int32_t *d_count,
+                int cap, int32_t *d_fail, int use_graph, void *stream) {
+  // argument errors first: none of them touches the plan or the GPU
+  if (!m || !d_q || !d_x || !d_y || !h_uniform || !d_stats_all || !d_samples || !d_freq || !d_count || !d_fail)
+    return pyz_fail(PYZ_E_INVALID, "pyz_hmc_run: null pointer");
+  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "pyz_hmc_run: n_steps must be positive");
+  if (n_burn < 0 || n_burn > n_steps) return pyz_fail(PYZ_E_INVALID, "pyz_hmc_run: n_burn %d outside [0, %d]", n_burn, n_steps);
+  if (cap < 1) return pyz_fail(PYZ_E_INVALID, "pyz_hmc_run: cap must be at least 1 (the starting q is a row)");
+  if (step0 < 0) return pyz_fail(PYZ_E_INVALID, "pyz_hmc_run: negative step0");
+  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "pyz_hmc_run: slot0 out of range");
+  int rc = check_call(m, P, n_rows);
+  if (rc) return rc;
+  if ((rc = check_loss_combo(m))) return rc;
+  if (L < 0) return pyz_fail(PYZ_E_INVALID, "L must be >= 0");
+  if (m->D > 0x7fffffff / 2) return pyz_fail(PYZ_E_SHAPE, "pyz_hmc_run: the model is too large for the sample record's indexing");
+  hipStream_t st = as_stream(stream);
+  pyz_mlp_full *f = full(m);
+  Extra &x = f->x;
+  // ---- the run's device words and the uniform table
+  const size_t snap_off = 256, stats_off = snap_off + (sizeof(int32_t) * (size_t)m->max_p + 63) / 64 * 64;
+  if (!x.hr_buf) {
+    size_t have = 0;
+    if ((rc = ensure_bytes(&x.hr_buf, &have, stats_off + sizeof(float) * 8 * (size_t)m->max_p, m))) return rc;
+  }
+  static_assert(sizeof(HmcRunCtl) <= 256, "HmcRunCtl outgrew its slot");
+  HmcRunArgs ra{};
+  ra.ctl = reinterpret_cast<HmcRunCtl *>(x.hr_buf);
+  ra.snap_count = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(x.hr_buf) + snap_off);
+  float *run_stats = reinterpret_cast<float *>(static_cast<unsigned char *>(x.hr_buf) + stats_off);
+  ra.unif = m->scal + 9 * m->max_p;                                   // the slot pyz_hmc_step uploads to
+  ra.call = reinterpret_cast<HmcCall *>(m->scal + 10 * m->max_p);
+  ra.q = d_q;
+  ra.stats = run_stats;
+  ra.nonfinite = m->nonfinite;
+  ra.P = P;
+  ra.D = (int)m->D;
+  const size_t n_tab = (size_t)n_steps * P;
+  if (x.hr_tab_cap < n_tab) {   // (the table's address is a word of HmcRunCtl, not baked into the graphs)
+    if (x.hr_tab) {
+      PYZ_HIP(hipDeviceSynchronize());   // (rare: an earlier run on another stream may still read it)
+      PYZ_HIP(hipFree(x.hr_tab));
+      x.hr_tab = nullptr;
+      x.hr_tab_cap = 0;
+    }
+    const size_t cap_f = std::max<size_t>(n_tab, 16384);
+    PYZ_HIP(hipMalloc((void **)&x.hr_tab, sizeof(float) * cap_f));
+    m->ws_bytes += sizeof(float) * cap_f;
+    x.hr_tab_cap = cap_f;
+  }
+  if (x.hr_host_cap < sizeof(float) * n_tab) {
+    if (x.hr_host) {
+      PYZ_HIP(hipDeviceSynchronize());
+      PYZ_HIP(hipHostFree(x.hr_host));
+      x.hr_host = nullptr;
+    } else {
+      for (auto &e : x.hr_ev) PYZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const size_t cap_b = std::max<size_t>(sizeof(float) * n_tab, 65536);
+    PYZ_HIP(hipHostMalloc((void **)&x.hr_host, 2 * cap_b));
+    x.hr_host_cap = cap_b;
+    x.hr_count = 0;
+  }
+  {
+    const unsigned slot = (unsigned)(x.hr_count & 1);
+    if (x.hr_count >= 2) PYZ_HIP(hipEventSynchronize(x.hr_ev[slot]));   // the copy of the run before the previous one has left
+    ++x.hr_count;
+    unsigned char *hb = x.hr_host + slot * x.hr_host_cap;
+    std::memcpy(hb, h_uniform, sizeof(float) * n_tab);
+    PYZ_HIP(hipMemcpyAsync(x.hr_tab, hb, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
+    PYZ_HIP(hipEventRecord(x.hr_ev[slot], st));
+  }
+  HmcRunCtl init{};
+  init.unif_tab = x.hr_tab;
+  init.stats_all = d_stats_all;
+  init.samples = d_samples;
+  init.freq = d_freq;
+  init.count = d_count;
+  init.fail = d_fail;
+  init.seed = seed;
+  init.step0 = step0;
+  init.slot0 = slot0;
+  init.n_burn = n_burn;
+  init.cap = cap;
+  PYZ_LAUNCH(k_hmc_run_begin, dim3(1), dim3(1), 0, st, ra.ctl, init);
+
+  const dim3 rgrid(cdiv(cdiv(m->D, 4), 256), P);
+  struct Fed {   // pyz_hmc_step below takes its scalars from the device; whatever way this call ends, the next one uploads again
+    bool &on;
+    explicit Fed(bool &b) : on(b) { on = true; }
+    ~Fed() { on = false; }
+  } fed(x.hm_fed);
+  auto proposal = [&](int i) -> int {
+    PYZ_LAUNCH(k_hmc_feed, rgrid, dim3(256), 0, st, ra);
+    const int prc = pyz_hmc_step(m, d_q, P, d_x, d_y, n_rows, L, epsilon, mass, prior_mean, prior_sigma, d_prior_mean_vec,
+                                 d_prior_sigma_vec, i < n_burn ? 1 : 0, h_uniform, step0 + i, seed, nullptr, run_stats, stream);
+    if (prc) return prc;
+    PYZ_LAUNCH(k_hmc_record, rgrid, dim3(256), 0, st, ra);
+    return PYZ_OK;
+  };
+  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  x.hr_captures = 0;
+  int s = 0;
+  if ((rc = proposal(s))) return rc;
+  ++s;
+  ++m->run_eager_steps;
+  const int G = std::min(256, std::max(1, pyz_env_int("PYZ_HMC_RUN_CHUNK", 16)));   // (read per call, mixed into the key)
+  if (use_graph && st != nullptr && !pyz_probe().on && x.hm_path >= 2) {
+    // everything baked into the graphs goes into the key: what the sliced launches bake in (hm_sig: kernel, shapes,
+    // pointers, scalars, stream) and the arguments of the feed / record launches
+    unsigned long long key = x.hm_sig;
+    auto mix = [&](unsigned long long v) { key = (key ^ v) * 1099511628211ull; };
+    mix((unsigned long long)(uintptr_t)x.hr_buf); mix((unsigned long long)(uintptr_t)ra.unif); mix((unsigned long long)m->max_p);
+    mix((unsigned long long)m->D); mix((unsigned long long)G);
+    if (x.hr_key != key) {
+      drop_hmc_run_graphs(x);
+      x.hr_key = key;
+    }
+    while (s < n_steps) {
+      const int len = std::min(G, n_steps - s);
+      int ci = 0;
+      if (len < G) {  // the remainder: its own graph, by exact length
+        ci = -1;
+        int free_slot = -1, lru = -1;
+        for (int c = 1; c < PYZ_GRAPH_CHUNKS; ++c) {
+          if (!x.hr_exec[c]) {
+            if (free_slot < 0) free_slot = c;
+            continue;
+          }
+          if (x.hr_len[c] == len) ci = c;
+          if (lru < 0 || x.hr_use[c] < x.hr_use[lru]) lru = c;
+        }
+        if (ci < 0) {
+          ci = free_slot >= 0 ? free_slot : lru;
+          if (x.hr_exec[ci]) (void)hipGraphExecDestroy(x.hr_exec[ci]);
+          if (x.hr_graph[ci]) (void)hipGraphDestroy(x.hr_graph[ci]);
+          x.hr_exec[ci] = nullptr;
+          x.hr_graph[ci] = nullptr;
+        }
+      }
+      if (!x.hr_exec[ci]) {
+        PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        int crc = PYZ_OK;
+        for (int k = 0; k < len && !crc; ++k) crc = proposal(s + k);   // (step and burning ride in HmcCall: the graph fits any position)
+        hipGraph_t gr = nullptr;
+        const hipError_t ce = hipStreamEndCapture(st, &gr);
+        if (crc || ce != hipSuccess) {
+          if (gr) (void)hipGraphDestroy(gr);
+          return crc ? crc : pyz_fail(PYZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+        }
+        x.hr_graph[ci] = gr;
+        PYZ_HIP(hipGraphInstantiate(&x.hr_exec[ci], gr, nullptr, nullptr, 0));
+        x.hr_len[ci] = len;
+        ++x.hr_captures;
+      }
+      x.hr_use[ci] = ++x.hr_clock;
+      PYZ_HIP(hipGraphLaunch(x.hr_exec[ci], st));
+      s += len;
+      m->run_graph_steps += len;
+      ++m->run_graph_launches;
+    }
+  }
+  for (; s < n_steps; ++s) {
+    if ((rc = proposal(s))) return rc;
+    ++m->run_eager_steps;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_hmc_run_info(const pyz_mlp *m, int32_t *h_captures) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (h_captures) *h_captures = static_cast<const pyz_mlp_full *>(m)->x.hr_captures;
   return PYZ_OK;
 }
 

@@ -478,3 +478,118 @@ __global__ void __launch_bounds__(PYZ_HM_THREADS) k_hmc_resident(HmcMultiArgs m)
     m.epoch[chain] = epoch0 + (unsigned)L + 1u;
   }
 }
+
+// ---------------------------------------------------------------- pyz_hmc_run: consecutive proposals without host work
+// Everything that changes from proposal to proposal of a run lives in device memory (as StepCtl does for pyz_sgld_run):
+// k_hmc_feed fills the slot pyz_hmc_step fills from the host (uniforms + HmcCall) from the run's uniform table,
+// k_hmc_record keeps the statistics of the proposal and the sample record of HMC.py:92-103.  Both run on a grid sized
+// to D (the copy of a q row); the words more than one workgroup reads are written behind a kernel boundary only:
+// k_hmc_feed reads the live words (cursor, count) and writes their snapshot, k_hmc_record reads the snapshot and
+// writes the live words.
+struct HmcRunCtl {
+  // the call (k_hmc_run_begin)
+  const float *unif_tab;  // (n_steps, P) uniforms of the call, proposal-major
+  float *stats_all;       // (slots, P, 8)
+  float *samples;         // (P, cap, D)
+  int32_t *freq;          // (P, cap)
+  int32_t *count;         // (P) live: rows recorded per chain
+  int32_t *fail;          // (4) {chains that ran out of rows, proposals that gave up, non-finite losses, proposals done}
+  uint64_t seed;
+  long long step0, slot0;
+  int n_burn, cap;
+  int cursor;             // live: the proposal of the call about to run
+  int snap_cursor;        // the proposal in flight (k_hmc_feed -> k_hmc_record)
+};
+
+struct HmcRunArgs {
+  HmcRunCtl *ctl;
+  int32_t *snap_count;    // (P) count[] as k_hmc_feed found it
+  float *unif;            // the plan's slot: (max_p) uniforms ...
+  HmcCall *call;          // ... and the HmcCall behind them
+  const float *q;         // (P, D)
+  const float *stats;     // (P, 8) of the proposal that just ran
+  int *nonfinite;         // the plan's sentinel (pyz_check_finite)
+  int P, D;
+};
+
+__global__ void k_hmc_run_begin(HmcRunCtl *ctl, HmcRunCtl init) { *ctl = init; }
+
+// four elements per thread of one row; 16-byte loads and stores when the rows allow it
+__device__ __forceinline__ void pyz_hm_copy_row(float *dst, const float *src, const int D) {
+  const int e0 = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (e0 >= D) return;
+  if ((D & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0) {   // (uniform)
+    *reinterpret_cast<float4 *>(dst + e0) = *reinterpret_cast<const float4 *>(src + e0);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (e0 + j < D) dst[e0 + j] = src[e0 + j];
+  }
+}
+
+// before proposal `cursor`: its uniforms and HmcCall; a chain without a row at its first sampling proposal gets its
+// starting q as row 0 (HMC.py:75-77; k_hmc_record counts it).  grid (ceil(D / 1024), P) x 256
+__global__ void __launch_bounds__(256) k_hmc_feed(HmcRunArgs g) {
+  HmcRunCtl *ctl = g.ctl;
+  const int c = blockIdx.y;
+  const int cur = ctl->cursor, burning = cur < ctl->n_burn ? 1 : 0;
+  const int cnt = ctl->count[c];
+  if (!burning && cnt == 0)
+    pyz_hm_copy_row(ctl->samples + (long long)c * ctl->cap * g.D, g.q + (long long)c * g.D, g.D);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    g.snap_count[c] = cnt;
+    g.unif[c] = ctl->unif_tab[(long long)cur * g.P + c];
+    if (c == 0) {
+      HmcCall hc;
+      hc.seed = ctl->seed;
+      hc.step = (uint32_t)(ctl->step0 + cur);
+      hc.burning = burning;
+      *g.call = hc;
+      ctl->snap_cursor = cur;
+    }
+  }
+}
+
+// after the proposal: its statistics to their slot, the sample record (HMC.py:92-103), the failure words, the cursor
+__global__ void __launch_bounds__(256) k_hmc_record(HmcRunArgs g) {
+  HmcRunCtl *ctl = g.ctl;
+  const int c = blockIdx.y;
+  const int cur = ctl->snap_cursor, cap = ctl->cap;
+  const bool burning = cur < ctl->n_burn;
+  const int cnt = g.snap_count[c];
+  const float *s = g.stats + c * 8;
+  const bool acc = s[0] != 0.0f, gave_up = s[7] < 0.0f;
+  const bool lead = blockIdx.x == 0;
+  if (lead && threadIdx.x < 8) ctl->stats_all[((ctl->slot0 + cur) * g.P + c) * 8 + threadIdx.x] = s[threadIdx.x];
+  const bool rec = !burning && !gave_up;
+  const int base = cnt == 0 ? 1 : cnt;          // (row 0 of a fresh chain is the starting q, cap >= 1)
+  const bool fits = base < cap;
+  if (rec && acc && fits) pyz_hm_copy_row(ctl->samples + ((long long)c * cap + base) * g.D, g.q + (long long)c * g.D, g.D);
+  if (lead && threadIdx.x == 0) {
+    if (rec) {
+      int32_t *fr = ctl->freq + (long long)c * cap;
+      if (cnt == 0) fr[0] = 1;
+      if (base > cap) {                         // (a count the caller brought: outside the record)
+        atomicAdd(ctl->fail + 0, 1);
+      } else if (!acc) {
+        fr[base - 1] += 1;
+        ctl->count[c] = base;
+      } else if (fits) {
+        fr[base] = 1;
+        ctl->count[c] = base + 1;
+      } else {                                  // out of rows: nothing recorded, the caller reads the word
+        ctl->count[c] = base;
+        atomicAdd(ctl->fail + 0, 1);
+      }
+    }
+    if (gave_up) atomicAdd(ctl->fail + 1, 1);
+    else if (!isfinite(s[1])) {
+      atomicAdd(ctl->fail + 2, 1);
+      atomicAdd(g.nonfinite, 1);
+    }
+    if (c == 0) {
+      atomicAdd(ctl->fail + 3, 1);
+      ctl->cursor = cur + 1;
+    }
+  }
+}

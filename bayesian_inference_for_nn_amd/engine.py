@@ -361,6 +361,47 @@ class MLPPlan:
                                     1 if burning else 0, u.ctypes.data_as(C.POINTER(C.c_float)), int(step), int(seed),
                                     ptr(unit_p), ptr(stats_out), _stream()))
 
+    def hmc_run(self, q, x, y, L, epsilon, m, prior_mean, prior_sigma, uniforms, n_burn, step0, seed, stats_all, samples,
+                freq, count, fail, use_graph=True, slot0=0, prior_mean_vec=None, prior_sigma_vec=None):
+        """len(uniforms) / P consecutive proposals of hmc_step without host work in between.  uniforms: host float32
+        (n_steps, P), proposal-major; the first n_burn proposals burn and record nothing; proposal i writes its
+        statistics to stats_all[slot0 + i] (slots, P, 8).  The sample record stays on the device: samples float32
+        (P, cap, D), freq int32 (P, cap), count int32 (P,) (zeros for a fresh record), fail int32 (4,) (zeroed by the
+        caller): {accepted proposals without a row, give-ups, non-finite losses, proposals done}."""
+        P = 1 if q.dim() == 1 else q.shape[0]
+        _f32(q, name="q")
+        assert q.numel() == P * self.D
+        for t, nm in ((prior_mean_vec, "prior_mean_vec"), (prior_sigma_vec, "prior_sigma_vec")):
+            if t is not None:
+                _f32(t, (self.D,), nm)
+        n_rows = x.shape[0]
+        self._check_xy(x, y, None, n_rows)
+        u = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float32).reshape(-1))
+        if u.size == 0 or u.size % P:
+            raise ValueError("uniforms must hold n_steps x P values")
+        n_steps = u.size // P
+        _f32(stats_all, name="stats_all")
+        _f32(samples, name="samples")
+        if samples.dim() != 3 or samples.shape[0] != P or samples.shape[2] != self.D:
+            raise ValueError("samples must be (P, cap, D)")
+        cap = int(samples.shape[1])
+        for t, nm, n in ((freq, "freq", P * cap), (count, "count", P), (fail, "fail", 4)):
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() < n:
+                raise ValueError(f"{nm} must be a contiguous int32 device tensor of at least {n} entries")
+        if slot0 < 0 or stats_all.numel() < (slot0 + n_steps) * P * 8:
+            raise ValueError("stats_all must hold (slot0 + n_steps) * P * 8 entries")
+        check(self.lib.pyz_hmc_run(self.h, ptr(q), P, ptr(x), ptr(y), n_rows, int(L), float(epsilon), float(m),
+                                   float(prior_mean), float(prior_sigma), ptr(prior_mean_vec), ptr(prior_sigma_vec),
+                                   u.ctypes.data_as(C.POINTER(C.c_float)), n_steps, int(n_burn), int(step0), int(slot0),
+                                   int(seed), ptr(stats_all), ptr(samples), ptr(freq), ptr(count), cap, ptr(fail),
+                                   1 if use_graph else 0, _stream()))
+
+    def hmc_run_captures(self) -> int:
+        """Graphs the last hmc_run call on this plan had to capture (0: every chunk was replayed from the cache)."""
+        n = C.c_int32()
+        check(self.lib.pyz_hmc_run_info(self.h, C.byref(n)))
+        return n.value
+
     # ------------------------------------------------------------------ V2-V4
     def svgd_step(self, particles, all_particles, row0, adam_m, adam_v, x, y, lr, gamma, t, loss_out, sweep="gauss_seidel",
                   batch=None, row_idx=None):

@@ -1,7 +1,16 @@
 """Hamiltonian Monte Carlo on the full training split (mirrors Pyesian/optimizers/HMC.py:13-187).
 Hyperparameters: m, L, epsilon; kwarg prior (GaussianPrior).  Extension: kwarg n_chains runs
-that many independent chains in one particle-batched launch (the reference has one)."""
+that many independent chains in one particle-batched launch (the reference has one).
 
+A quiet train() (verbose off) is one device-resident run (pyz_hmc_run): every uniform of the burn-in and the sampling
+proposals is drawn up front with random.random() in the step loop's order, the proposals run back to back on the
+optimizer's stream with the sample record of HMC.py:92-103 kept on the device ((n_chains, nb_iterations + 1, D) rows,
+their frequencies and counts), and after ONE join `fold_run_record` rebuilds the chain lists, the counters and
+last_stats exactly as the step loop leaves them.  The step loop is taken instead when PYZ_HMC_RUN=0, when the record
+would exceed PYZ_HMC_RUN_MAX_BYTES (default 1 GiB), or when the library refuses the shape; step(), a verbose train(),
+result() and the multi-rank merge are the same either way."""
+
+import os
 import random
 
 import numpy as np
@@ -9,6 +18,33 @@ import numpy as np
 from ..distributions import Sampled
 from ..nn import BayesianModel
 from .Optimizer import DeviceScalar, Optimizer
+
+
+GAVE_UP = ("an HMC proposal gave up waiting for its row-slice workgroups (k_hmc_resident: the grid was not "
+           "resident at once); set PYZ_HMC_RESIDENT=0 for one launch per gradient evaluation")
+
+
+def fold_run_record(stats_all, count, freq, samples):
+    """The device record of a run's sampling proposals as the step loop's bookkeeping (HMC.py:75-77, 92-103).
+    stats_all: (n, P, 8) statistics of the n sampling proposals; count: (P,) rows recorded per chain; freq: (P, cap);
+    samples: per chain, a sequence of at least count[c] rows.  Returns (chain_samples, chain_freq, accepted_runs,
+    total_runs): per chain the first count[c] rows and their frequencies as lists, the accepted proposals of chain 0
+    and n.  The record must be the one the statistics describe: a chain has 1 + its accepted proposals as rows (none
+    before the first sampling proposal) and its frequencies add up to 1 + n."""
+    stats_all = np.asarray(stats_all)
+    n, P = stats_all.shape[0], stats_all.shape[1]
+    chain_samples, chain_freq = [], []
+    for c in range(P):
+        k = int(count[c])
+        accepted = int(np.count_nonzero(stats_all[:, c, 0])) if n else 0
+        fr = [int(v) for v in np.asarray(freq[c])[:k]]
+        if k != (1 + accepted if n else 0) or sum(fr) != (1 + n if n else 0):
+            raise RuntimeError(f"HMC run: chain {c} recorded {k} rows with frequencies adding up to {sum(fr)}; its {n} "
+                               f"proposals accepted {accepted}")
+        chain_samples.append([samples[c][i] for i in range(k)])
+        chain_freq.append(fr)
+    accepted_runs = int(np.count_nonzero(stats_all[:, 0, 0])) if n else 0
+    return chain_samples, chain_freq, accepted_runs, n
 
 
 class HMC(Optimizer):
@@ -101,8 +137,7 @@ class HMC(Optimizer):
         self._stream.synchronize()
         all_stats = torch.stack([p[0] for p in self._pending]).cpu().numpy()
         if (all_stats[:, :, 7] < 0).any():
-            raise RuntimeError("an HMC proposal gave up waiting for its row-slice workgroups (k_hmc_resident: the grid was not "
-                               "resident at once); set PYZ_HMC_RESIDENT=0 for one launch per gradient evaluation")
+            raise RuntimeError(GAVE_UP)
         for (_, q_snap, sampling), stats in zip(self._pending, all_stats):
             accepted = stats[:, 0] != 0
             if accepted[0]:
@@ -122,6 +157,8 @@ class HMC(Optimizer):
               model_save_path: str = None):
         import torch
         self._resolve_pending()
+        if not self._verbose and self._train_resident(nb_iterations):
+            return
         self._defer = True
         self._stream.wait_stream(torch.cuda.current_stream())
         try:
@@ -156,6 +193,52 @@ class HMC(Optimizer):
                                      accept_rate=accept_rate, bar_length=20)
         self._new_progress_line()
         self._resolve_pending()
+
+    def _train_resident(self, nb_iterations: int) -> bool:
+        """_train as one pyz_hmc_run (see the module docstring).  False: no proposal has run, q is untouched and no
+        uniform is consumed; the step loop has to run."""
+        import torch
+        from .._lib import PyzError
+        if os.environ.get("PYZ_HMC_RUN", "1") == "0":
+            return False
+        P, D = self._n_chains, int(self._q.shape[1])
+        nb_burn, n = int(self._nb_burn_epoch), max(int(nb_iterations), 0)
+        cap = n + 1
+        if nb_burn + n <= 0 or 4 * P * cap * D > int(os.environ.get("PYZ_HMC_RUN_MAX_BYTES", str(1 << 30))):
+            return False
+        rng_state = random.getstate()
+        uniforms = [[random.random() for _ in range(P)] for _ in range(nb_burn + n)]     # HMC.py:91, the step loop's order
+        self._stream.wait_stream(torch.cuda.current_stream())
+        try:
+            with torch.cuda.stream(self._stream):
+                stats_all = torch.zeros((nb_burn + n, P, 8), device="cuda")
+                samples = torch.empty((P, cap, D), device="cuda")
+                freq = torch.zeros((P, cap), dtype=torch.int32, device="cuda")
+                count = torch.zeros((P,), dtype=torch.int32, device="cuda")
+                fail = torch.zeros((4,), dtype=torch.int32, device="cuda")
+                self._plan.hmc_run(self._q, self._x_dev, self._y_dev, int(self._L), self._epsilon, self._m, self._prior_mean,
+                                   self._prior_sigma, uniforms, nb_burn, self._step_count, self._seed, stats_all, samples,
+                                   freq, count, fail, prior_mean_vec=self._pm_vec, prior_sigma_vec=self._ps_vec)
+        except PyzError as e:
+            if e.code not in (-1, -2):                        # (an argument or shape the library refuses: no proposal has run, q is untouched)
+                raise
+            random.setstate(rng_state)
+            return False
+        self._stream.synchronize()                            # the one join of the run
+        torch.cuda.current_stream().wait_stream(self._stream)
+        self._step_count += nb_burn + n
+        stats_host, fail_host = stats_all.cpu().numpy(), fail.cpu().numpy()
+        if fail_host[1] > 0 or (stats_host[:, :, 7] < 0).any():
+            raise RuntimeError(GAVE_UP)
+        if fail_host[0] > 0:
+            raise RuntimeError("HMC run: the sample record ran out of rows")
+        count_host = count.cpu().numpy()
+        rows = [samples[c, :int(count_host[c])].clone() for c in range(P)]     # (the record itself is released)
+        self._chain_samples, self._chain_freq, self._accepted_runs, self._total_runs = fold_run_record(
+            stats_host[nb_burn:], count_host, freq.cpu().numpy(), rows)
+        self.last_stats = stats_host[-1]
+        self._frequency, self._samples = self._chain_freq[0], self._chain_samples[0]
+        return True
 
     def update_parameters_step(self):
         pass

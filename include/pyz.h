@@ -256,6 +256,37 @@ int pyz_hmc_step(pyz_mlp *mlp, float *d_q, int n_chains, const float *d_x, const
                  int burning, const float *h_uniform, int64_t step, uint64_t seed,
                  const float *d_unit_p, float *d_stats, void *stream);
 
+/* The quiet HMC.train (HMC.py:106-125) as ONE device-resident run: n_steps consecutive proposals of pyz_hmc_step
+ * (same model, data, L, epsilon, m and prior; momentum from Philox) with no host work in between.  h_uniform
+ * (host, float32 [n_steps x n_chains], proposal-major: the random.random() draws in the reference's order) is
+ * uploaded once; proposal i of the call uses Philox step step0 + i, runs with burning = 1 and records nothing while
+ * i < n_burn, and writes its eight statistics (the layout of pyz_hmc_step's d_stats, stats[7] = -1 on a give-up) to
+ * d_stats_all[(slot0 + i) * n_chains * 8 ..].  The sample record of HMC.py:92-103 is kept on the device: d_samples
+ * float32 (n_chains, cap, D), d_freq int32 (n_chains, cap), d_count int32 [n_chains] (zero for a fresh record; a
+ * later call goes on where the counts stand).  After a non-burning proposal an accepted chain c gets
+ * d_samples[c][count] = q[c], d_freq[c][count] = 1, count += 1, a rejected one d_freq[c][count - 1] += 1; a chain
+ * with count == 0 first records its starting q with frequency 1 (HMC.py:75-77); a proposal that gave up records
+ * nothing; a chain out of rows records nothing and counts in d_fail, never writing past cap rows.  d_fail int32 [4]
+ * (the caller zeroes it; counts add up over calls) = {accepted proposals that found no row, proposals (per chain)
+ * that gave up, non-finite losses, proposals done}.  With use_graph != 0 on a non-NULL stream the sliced forms
+ * (at most 16 chains, >= 192 rows) replay hipGraphs of 16 proposals (PYZ_HMC_RUN_CHUNK) and one of the exact
+ * remaining length, captured once per length and kept; the one-workgroup form and the generic sequence are launched
+ * eagerly, still without a synchronisation; the first proposal of a call is always eager.  pyz_last_run_info
+ * reports the split of the last call, pyz_hmc_run_info the graphs it had to capture.  Argument errors (a NULL
+ * pointer, n_steps <= 0, n_burn outside [0, n_steps], cap < 1, negative step0 / slot0) return PYZ_E_INVALID before
+ * anything touches the GPU.  q, every proposal's statistics and the accept sequence equal n_steps calls of
+ * pyz_hmc_step bit for bit.  A non-finite loss of a proposal also counts in the plan's sentinel (pyz_check_finite; the
+ * generic sequence counts there per gradient evaluation as well); give-ups and chains out of rows are reported in
+ * d_fail only.  As with every entry point, one host thread drives a plan at a time: the run calls pyz_hmc_step's dispatch
+ * on the plan, which must not be entered from another thread meanwhile.  pyz_hmc_run_info: *h_captures = the graphs the
+ * last pyz_hmc_run on the plan had to capture (0: every chunk was replayed from the cache). */
+int pyz_hmc_run(pyz_mlp *mlp, float *d_q, int n_chains, const float *d_x, const void *d_y, int n_rows, int L,
+                float epsilon, float m, float prior_mean, float prior_sigma, const float *d_prior_mean_vec,
+                const float *d_prior_sigma_vec, const float *h_uniform, int n_steps, int n_burn, int64_t step0,
+                int64_t slot0, uint64_t seed, float *d_stats_all, float *d_samples, int32_t *d_freq,
+                int32_t *d_count, int cap, int32_t *d_fail, int use_graph, void *stream);
+int pyz_hmc_run_info(const pyz_mlp *mlp, int32_t *h_captures);
+
 /* ---- V2-V4: SVGD.step (SVGD.py:84-141).  d_particles (P_local, D) float32 are
  * this rank's rows [row0, row0+P_local) of the (M, D) particle matrix; d_all
  * (M, D) is the matrix the kernel row is evaluated against (== d_particles on
