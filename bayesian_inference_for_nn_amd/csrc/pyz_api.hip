@@ -49,6 +49,20 @@ struct Extra {  // lazily sized buffers kept beside the plan
   size_t tab_host_cap = 0;  // bytes per buffer
   hipEvent_t tab_ev[2] = {};
   unsigned long long tab_count = 0;
+  // pyz_adam_run: the bias-correction pairs beside tab_bs / tab_lr, and what each cached graph was captured for (a graph
+  // of these runs bakes in the launch geometry of every step: the batch sizes of its chunk)
+  float2 *tab_bc = nullptr;
+  int tab_bc_cap = 0;
+  // ... and these runs' own graph cache.  A graph holds steps of one batch size and starts on one StepCtl slot, and a quiet
+  // train() cuts its stretches of equal batches wherever its resident chunks end: stretch lengths 1 .. batches per epoch in
+  // two parities, plus the ragged batch.  AR_GRAPHS slots keep all of them for epochs of up to ~14 batches; longer epochs
+  // mostly see full chunks.  ar_captures: graphs the last call had to capture (pyz_adam_run_info).
+  static constexpr int AR_GRAPHS = 32;
+  hipGraph_t ar_graph[AR_GRAPHS] = {};
+  hipGraphExec_t ar_exec[AR_GRAPHS] = {};
+  int ar_len[AR_GRAPHS] = {};
+  unsigned long long ar_sig[AR_GRAPHS] = {}, ar_use[AR_GRAPHS] = {}, ar_clock = 0, ar_key = 0;
+  int ar_captures = 0;
   // per-proposal HMC scalars (uniforms + HmcCall) go up through a ring of pinned slots: a copy from pageable
   // memory would make every pyz_hmc_step wait for the stream, i.e. serialise the host with the device
   static constexpr int UP_SLOTS = 64;
@@ -92,6 +106,16 @@ void drop_hmc_run_graphs(Extra &x) {
     x.hr_exec[c] = nullptr;
     x.hr_graph[c] = nullptr;
     x.hr_len[c] = 0;
+  }
+}
+
+void drop_adam_run_graphs(Extra &x) {
+  for (int c = 0; c < Extra::AR_GRAPHS; ++c) {
+    if (x.ar_exec[c]) (void)hipGraphExecDestroy(x.ar_exec[c]);
+    if (x.ar_graph[c]) (void)hipGraphDestroy(x.ar_graph[c]);
+    x.ar_exec[c] = nullptr;
+    x.ar_graph[c] = nullptr;
+    x.ar_len[c] = 0;
   }
 }
 
@@ -734,11 +758,12 @@ int pyz_mlp_destroy(pyz_mlp *mm) {
   if (m->x.hm_exec) (void)hipGraphExecDestroy(m->x.hm_exec);
   if (m->x.hm_graph) (void)hipGraphDestroy(m->x.hm_graph);
   drop_hmc_run_graphs(m->x);
+  drop_adam_run_graphs(m->x);
   for (int l = 0; l < PYZ_MAX_LAYERS; ++l) {
     if (m->act[l]) (void)hipFree(m->act[l]);
     if (m->delta[l]) (void)hipFree(m->delta[l]);
   }
-  void *ptrs[] = {m->grad, m->grad2, m->qsave, m->part, m->x.part2, m->scal, m->ctl, m->tab_bs, m->xb, m->x.hm_buf, m->x.hm_res_buf, m->x.gs_res_buf, m->x.fwd_part, m->nonfinite, m->x.hr_buf, m->x.hr_tab};
+  void *ptrs[] = {m->grad, m->grad2, m->qsave, m->part, m->x.part2, m->scal, m->ctl, m->tab_bs, m->xb, m->x.hm_buf, m->x.hm_res_buf, m->x.gs_res_buf, m->x.fwd_part, m->nonfinite, m->x.hr_buf, m->x.hr_tab, m->x.tab_bc};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (m->x.tab_host) {
@@ -979,6 +1004,39 @@ struct BbbChain {  // chained BBB run: what the step needs beside mu (= theta), 
   float *val_losses;        // [slot] per step; written on the steps that validate (BBB.py:203: step % 10 != 0)
 };
 
+// per-run tables of the device-resident runs (n_tab entries: one padding entry, the last step prepares a slot nobody reads):
+// batch sizes and learning rates share one device allocation; host_entry_bytes = what one entry takes in the pinned
+// staging buffers (8; 16 with pyz_adam_run's bias-correction pairs)
+static int ensure_run_tables(pyz_mlp *m, size_t n_tab, size_t host_entry_bytes, hipStream_t st) {
+  pyz_mlp_full *f = full(m);
+  if (m->tab_cap < (int)n_tab) {
+    const size_t cap = std::max<size_t>(n_tab, 65536);  // generous: the table pointers are baked into the graphs
+    if (m->tab_bs) PYZ_HIP(hipFree(m->tab_bs));
+    m->tab_bs = nullptr;
+    m->tab_lr = nullptr;
+    PYZ_HIP(hipMalloc((void **)&m->tab_bs, 8 * cap));
+    m->tab_lr = reinterpret_cast<float *>(m->tab_bs + cap);
+    m->tab_cap = (int)cap;
+    drop_graphs(m);
+  }
+  // the tables go up through two pinned buffers used in turn: a buffer is rewritten once the copy of the run
+  // before the previous one has left it (no stream-wide synchronisation per call)
+  if (f->x.tab_host_cap < host_entry_bytes * n_tab) {
+    if (f->x.tab_host) {
+      PYZ_HIP(hipStreamSynchronize(st));
+      PYZ_HIP(hipHostFree(f->x.tab_host));
+      f->x.tab_host = nullptr;
+    } else {
+      for (auto &e : f->x.tab_ev) PYZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const size_t cap = std::max<size_t>(host_entry_bytes * n_tab, host_entry_bytes * 4096);
+    PYZ_HIP(hipHostMalloc(&f->x.tab_host, 2 * cap));
+    f->x.tab_host_cap = cap;
+    f->x.tab_count = 0;
+  }
+  return PYZ_OK;
+}
+
 static void launch_sgld_step(pyz_mlp *m, float *theta, float *mean, float *sq, const float *x, const void *y,
                              const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
                              uint64_t seed, const float *unit_noise, float *loss, hipStream_t st, int mode = PYZ_UPD_SGLD,
@@ -1157,31 +1215,7 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
   // per-run tables (one padding entry: the last step prepares a slot nobody reads); batch sizes and learning
   // rates share one device allocation
   const size_t n_tab = (size_t)n_steps + 1;
-  if (m->tab_cap < (int)n_tab) {
-    const size_t cap = std::max<size_t>(n_tab, 65536);  // generous: the table pointers are baked into the graphs
-    if (m->tab_bs) PYZ_HIP(hipFree(m->tab_bs));
-    m->tab_bs = nullptr;
-    m->tab_lr = nullptr;
-    PYZ_HIP(hipMalloc((void **)&m->tab_bs, 8 * cap));
-    m->tab_lr = reinterpret_cast<float *>(m->tab_bs + cap);
-    m->tab_cap = (int)cap;
-    drop_graphs(m);
-  }
-  // the tables go up through two pinned buffers used in turn: a buffer is rewritten once the copy of the run
-  // before the previous one has left it (no stream-wide synchronisation per call)
-  if (f->x.tab_host_cap < 8 * n_tab) {
-    if (f->x.tab_host) {
-      PYZ_HIP(hipStreamSynchronize(st));
-      PYZ_HIP(hipHostFree(f->x.tab_host));
-      f->x.tab_host = nullptr;
-    } else {
-      for (auto &e : f->x.tab_ev) PYZ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const size_t cap = std::max<size_t>(8 * n_tab, 8 * 4096);
-    PYZ_HIP(hipHostMalloc(&f->x.tab_host, 2 * cap));
-    f->x.tab_host_cap = cap;
-    f->x.tab_count = 0;
-  }
+  if ((rc = ensure_run_tables(m, n_tab, 8, st))) return rc;
   const long long row_stride = m->max_batch;
   bool first_batch_done = false;
   if (n_steps <= PYZ_INLINE_TAB) {
@@ -1428,6 +1462,334 @@ int pyz_bbb_run(pyz_mlp *m, float *d_mu, float *d_rho, float *d_w, const float *
   bc.val_losses = d_val_losses;
   return sgld_run_impl(m, d_mu, d_rho, d_w, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, step0, slot0, seed, d_costs,
                        use_graph, stream, PYZ_UPD_BBB, nullptr, &bc);
+}
+
+// ---------------------------------------------------------------- ADAM / VADAM / BSAM train loops, device resident
+// ADAM.step / VADAM.step / BSAM.step inside Optimizer.train (ADAM.py:42-86, VADAM.py:45-99, BSAM.py:46-119,
+// Optimizer.py:121-134) as one device-resident run: sgld_run_impl's plumbing (StepCtl ping-pong, tab_bs / tab_lr, batches
+// assembled one step ahead, graphs of PYZ_GRAPH_STEPS steps and one of the exact remaining length) around the launch
+// sequence of pyz_adam_step / pyz_bsam_step, with the chained k_wgrad_adam / k_wgrad_bsam at the end of each pass.  Unlike the
+// SGLD run every step is launched for its OWN batch size, not for the largest of the call: the wave count of the
+// weight-gradient reduction (pyz_pick_waves) follows from it, and the results are to equal the eager steps bit for bit
+// on the ragged last batch of an epoch too.  A graph therefore holds steps of one batch size and is kept by its length, that
+// size and the StepCtl slot it starts on, in a cache of these runs' own (Extra::ar_*; the graphs of the other runs on the plan
+// stay); a call of equal batches is chunked exactly as in sgld_run_impl.
+struct AdamRunCfg {
+  bool bsam;
+  float *m, *v;
+  AdamScal as;         // ADAM / VADAM (lr, bc1, bc2 come per step)
+  BsamScal bs;         // BSAM (lr comes per step)
+  RunChain c;          // c.perturb: the perturbation of step i + 1 rides in step i's epilogue
+  bool perturbs;       // VADAM, BSAM
+  uint64_t seed;
+};
+
+static void launch_wgrad_adam_run(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl,
+                                  AdamRunArgs &a, hipStream_t st, const float *gathered) {
+  const int tiles = wgrad_layers(m, 1, x, row_idx, ctl, a.w, gathered);
+  const int S = pyz_pick_waves(tiles, (grid_batch + 1) / 2);
+  dim3 grid(tiles + 1);   // + the duties workgroup
+  if (a.w.prep.src) grid.x = (unsigned)(tiles + 1 + std::max(pyz_cu_count() - tiles - 1, 24));  // + the batch workers
+  switch (S) {
+    case 1: PYZ_LAUNCH((k_wgrad_adam<1, true>), grid, dim3(64), 0, st, a); break;
+    case 2: PYZ_LAUNCH((k_wgrad_adam<2, true>), grid, dim3(128), 2 * 4096, st, a); break;
+    case 4: PYZ_LAUNCH((k_wgrad_adam<4, true>), grid, dim3(256), 4 * 4096, st, a); break;
+    case 8: PYZ_LAUNCH((k_wgrad_adam<8, true>), grid, dim3(512), 8 * 4096, st, a); break;
+    default: PYZ_LAUNCH((k_wgrad_adam<16, true>), grid, dim3(1024), 16 * 4096, st, a); break;
+  }
+}
+
+static void launch_wgrad_bsam_run(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl,
+                                  int phase, BsamRunArgs &a, hipStream_t st, const float *gathered) {
+  const int tiles = wgrad_layers(m, 1, x, row_idx, ctl, a.w, gathered);
+  const int S = pyz_pick_waves(tiles, (grid_batch + 1) / 2);
+  dim3 grid(tiles + 1);   // + the duties workgroup
+  if (a.w.prep.src) grid.x = (unsigned)(tiles + 1 + std::max(pyz_cu_count() - tiles - 1, 24));  // + the batch workers
+#define PYZ_BSAM_CASE(W, LDS)                                                               \
+  if (phase == 0) PYZ_LAUNCH((k_wgrad_bsam<W, 0, true>), grid, dim3(64 * W), LDS, st, a);     \
+  else PYZ_LAUNCH((k_wgrad_bsam<W, 1, true>), grid, dim3(64 * W), LDS, st, a);                \
+  break
+  switch (S) {
+    case 1: PYZ_BSAM_CASE(1, 0);
+    case 2: PYZ_BSAM_CASE(2, 2 * 4096);
+    case 4: PYZ_BSAM_CASE(4, 4 * 4096);
+    case 8: PYZ_BSAM_CASE(8, 8 * 4096);
+    default: PYZ_BSAM_CASE(16, 16 * 4096);
+  }
+#undef PYZ_BSAM_CASE
+}
+
+// one step of the run on StepCtl slot `slot`, launched for its own batch size (the batch it assembles for the step behind it
+// is placed for the forward tiles of a full batch: placement only changes speed)
+static void launch_adam_run_step(pyz_mlp *m, const AdamRunCfg &c, float *theta, const float *x, const void *y,
+                                 const int32_t *row_idx, int grid_batch, int slot, long long row_stride, float *losses,
+                                 hipStream_t st) {
+  const StepCtl *ctl = m->ctl + slot;
+  const unsigned pgrid = (unsigned)cdiv(cdiv(m->D, 4), 256);
+  if (c.perturbs && !c.c.perturb) {   // PYZ_ADAM_FUSE_PERTURB=0: the step's perturbation as a launch of its own
+    if (c.bsam) PYZ_LAUNCH(k_bsam_perturb_run, dim3(pgrid), dim3(256), 0, st, theta, c.v, m->D, c.bs.inv_n, c.seed, ctl);
+    else PYZ_LAUNCH(k_vadam_perturb_run, dim3(pgrid), dim3(256), 0, st, theta, c.v, m->D, c.c.lam, c.c.num_data, c.seed, ctl);
+  }
+  const bool ahead = batch_ahead(m, row_idx);
+  static const int use_xb = pyz_env_int("PYZ_GATHER_COPY", 1);  // 1: forward leaves a contiguous batch copy
+  for (int phase = 0; phase < (c.bsam ? 2 : 1); ++phase) {
+    const float *rows;   // the contiguous rows of this step's batch that the weight-gradient kernel reads (or nullptr: gathered)
+    if (ahead) {
+      rows = batch_buf(m, slot);
+      launch_forward(m, theta, m->D, 1, rows, nullptr, grid_batch, ctl, st, nullptr, m->L - 1);
+    } else {
+      float *xb = (use_xb && m->L > 1) ? m->xb : nullptr;
+      rows = xb;
+      launch_forward(m, theta, m->D, 1, x, row_idx, grid_batch, ctl, st, xb, m->L - 1);
+    }
+    launch_head(m, theta, m->D, 1, x, y, row_idx, grid_batch, ctl, true, st);   // (labels go through row_idx)
+    launch_bwd_data_hidden(m, theta, m->D, 1, grid_batch, ctl, st);
+    const bool last = phase == (c.bsam ? 1 : 0);
+    WgradArgs w{};
+    w.mode = PYZ_UPD_NONE;
+    w.theta = theta;
+    w.loss = losses;
+    w.seed = c.seed;
+    w.next = m->ctl + (slot ^ 1);
+    w.tab_bs = m->tab_bs;
+    w.tab_lr = m->tab_lr;
+    w.row_stride = row_stride;
+    if (ahead && last) w.prep = prep_args(m, x, row_idx, m->max_batch, row_stride, slot ^ 1);
+    if (c.bsam) {
+      BsamRunArgs a{};
+      a.w = w;
+      a.m = c.m;
+      a.v = c.v;
+      a.g1 = m->grad2;
+      a.a = c.bs;
+      a.c = c.c;
+      launch_wgrad_bsam_run(m, x, row_idx, grid_batch, ctl, phase, a, st, rows);
+    } else {
+      AdamRunArgs a{};
+      a.w = w;
+      a.m = c.m;
+      a.v = c.v;
+      a.a = c.as;
+      a.c = c.c;
+      launch_wgrad_adam_run(m, x, row_idx, grid_batch, ctl, a, st, rows);
+    }
+  }
+}
+
+static int adam_run_impl(pyz_mlp *m, AdamRunCfg &c, float *d_theta, const float *d_x, const void *d_y,
+                         const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr, const int64_t *h_epochs,
+                         double beta_1, double beta_2, int n_steps, int64_t step0, int64_t slot0, float *d_losses,
+                         int use_graph, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (!can_fuse(m)) return pyz_fail(PYZ_E_INVALID, "the chained ADAM / VADAM / BSAM runs need a last layer of at most 32 units");
+  int rc = check_loss_combo(m);
+  if (rc) return rc;
+  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "n_steps must be positive");
+  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "slot0 out of range");
+  if (step0 < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
+  if (!d_theta || !c.m || !c.v || !d_x || !d_y || !d_row_idx || !h_batch_sizes || !h_lr || !d_losses || (!c.bsam && !h_epochs))
+    return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if (!(beta_1 >= 0.0 && beta_1 < 1.0) || !(beta_2 >= 0.0 && beta_2 < 1.0))
+    return pyz_fail(PYZ_E_INVALID, "beta_1 = %g, beta_2 = %g: both must lie in [0, 1)", beta_1, beta_2);
+  if (c.perturbs && !(c.c.num_data > 0.0f)) return pyz_fail(PYZ_E_INVALID, "num_data = %g must be positive", (double)c.c.num_data);
+  for (int s = 0; s < n_steps; ++s) {
+    if (h_batch_sizes[s] <= 0 || h_batch_sizes[s] > m->max_batch)
+      return pyz_fail(PYZ_E_SHAPE, "batch size %d of step %d outside [1, %d]", h_batch_sizes[s], s, m->max_batch);
+    if (!c.bsam && h_epochs[s] < 1) return pyz_fail(PYZ_E_INVALID, "epoch %lld of step %d < 1", (long long)h_epochs[s], s);
+  }
+  if (c.bsam && (rc = need_grad2(m, 1))) return rc;   // grad2 keeps the first pass's gradient
+  pyz_mlp_full *f = full(m);
+  hipStream_t st = as_stream(stream);
+  static const int fuse_perturb = pyz_env_int("PYZ_ADAM_FUSE_PERTURB", 1);
+  c.c.perturb = (c.perturbs && fuse_perturb) ? 1 : 0;
+
+  const size_t n_tab = (size_t)n_steps + 1;
+  if ((rc = ensure_run_tables(m, n_tab, c.bsam ? 8 : 16, st))) return rc;
+  if (!c.bsam && f->x.tab_bc_cap < m->tab_cap) {   // (as large as the other tables: its address is baked into the graphs too)
+    if (f->x.tab_bc) PYZ_HIP(hipFree(f->x.tab_bc));
+    f->x.tab_bc = nullptr;
+    f->x.tab_bc_cap = 0;
+    PYZ_HIP(hipMalloc((void **)&f->x.tab_bc, sizeof(float2) * (size_t)m->tab_cap));
+    f->x.tab_bc_cap = m->tab_cap;
+  }
+  c.c.tab_bc = c.bsam ? nullptr : f->x.tab_bc;
+  // 1 - beta^epoch of step s exactly as adam_scalars evaluates it for the eager step
+  auto bc_of = [&](int s) {
+    const AdamScal a = adam_scalars(0.0f, beta_1, beta_2, h_epochs[s], 0.0f, 0.0f);
+    return make_float2(a.bc1, a.bc2);
+  };
+  const long long row_stride = m->max_batch;
+  const bool ahead = batch_ahead(m, d_row_idx);
+  m->pend_on = false;
+  if (n_steps <= PYZ_INLINE_TAB) {   // short run: the tables ride in the arguments of the launch that sets the first step's scalars
+    InlineTabs tabs{};
+    InlineBc ibc{};
+    for (int s = 0; s <= n_steps; ++s) {
+      const int ss = std::min(s, n_steps - 1);
+      tabs.bs[s] = h_batch_sizes[ss];
+      tabs.lr[s] = h_lr[ss];
+      if (!c.bsam) ibc.bc[s] = bc_of(ss);
+    }
+    tabs.n = n_steps + 1;
+    const long long row_off = slot0 * row_stride;
+    if (ahead) {   // ... together with the first batch of the run
+      const PrepArgs pa = prep_args(m, d_x, d_row_idx, h_batch_sizes[0], row_stride, 0);
+      if (c.bsam) PYZ_LAUNCH(k_run_start, dim3(256), dim3(256), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)step0, row_off, (int)slot0, pa);
+      else PYZ_LAUNCH(k_run_start_bc, dim3(256), dim3(256), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, f->x.tab_bc, (long long)step0, row_off, (int)slot0, pa);
+    } else {
+      if (c.bsam) PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)step0, row_off, (int)slot0);
+      else PYZ_LAUNCH(k_set_ctl_tabs_bc, dim3(1), dim3(64), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, f->x.tab_bc, (long long)step0, row_off, (int)slot0);
+    }
+  } else {
+    const unsigned slot = (unsigned)(f->x.tab_count & 1);
+    if (f->x.tab_count >= 2) PYZ_HIP(hipEventSynchronize(f->x.tab_ev[slot]));
+    ++f->x.tab_count;
+    int32_t *hb = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(f->x.tab_host) + slot * f->x.tab_host_cap);
+    float *hl = reinterpret_cast<float *>(hb + n_tab);
+    float2 *hc = reinterpret_cast<float2 *>(hl + n_tab);   // (8 n_tab bytes in: aligned)
+    for (int s = 0; s <= n_steps; ++s) {
+      const int ss = std::min(s, n_steps - 1);
+      hb[s] = h_batch_sizes[ss];
+      hl[s] = h_lr[ss];
+      if (!c.bsam) hc[s] = bc_of(ss);
+    }
+    PYZ_HIP(hipMemcpyAsync(m->tab_bs, hb, sizeof(int32_t) * n_tab, hipMemcpyHostToDevice, st));
+    PYZ_HIP(hipMemcpyAsync(m->tab_lr, hl, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
+    if (!c.bsam) PYZ_HIP(hipMemcpyAsync(f->x.tab_bc, hc, sizeof(float2) * n_tab, hipMemcpyHostToDevice, st));
+    PYZ_HIP(hipEventRecord(f->x.tab_ev[slot], st));
+    if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], step0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
+    if (ahead)   // the first batch of the run (every later one is assembled by the step before it)
+      PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, h_batch_sizes[0], row_stride, 0), m->ctl);
+  }
+  // fused perturbation: only the first step of the call has nobody in front of it to perturb its weights
+  if (c.c.perturb) {
+    const unsigned pgrid = (unsigned)cdiv(cdiv(m->D, 4), 256);
+    if (c.bsam) PYZ_LAUNCH(k_bsam_perturb, dim3(pgrid), dim3(256), 0, st, d_theta, c.v, m->D, c.bs.inv_n, c.seed, (uint32_t)step0, (const float *)nullptr);
+    else PYZ_LAUNCH(k_vadam_perturb, dim3(pgrid), dim3(256), 0, st, d_theta, c.v, m->D, c.c.lam, c.c.num_data, c.seed, (uint32_t)step0, (const float *)nullptr);
+  }
+
+  auto step = [&](int s) {
+    launch_adam_run_step(m, c, d_theta, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, row_stride, d_losses, st);
+  };
+  int s = 0;
+  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  Extra &x = f->x;
+  x.ar_captures = 0;
+  const unsigned long long call_clock = x.ar_clock;   // graphs used after this stamp may still be in flight
+  static const int G = std::min(128, std::max(2, pyz_env_int("PYZ_GRAPH_STEPS", 32) & ~1));   // even: the chunks of a stretch start on one StepCtl slot
+  if (use_graph && st != nullptr && !pyz_probe().on) {
+    // everything baked into the graphs goes into the key (but the batch sizes: they go into each graph's own signature)
+    unsigned long long key = 1469598103934665603ull;
+    auto mix = [&](unsigned long long v) { key = (key ^ v) * 1099511628211ull; };
+    auto mixf = [&](float v) { unsigned b; memcpy(&b, &v, 4); mix(b); };
+    mix(c.bsam ? 0xb5a3ull : 0xada3ull);
+    mix((unsigned long long)(uintptr_t)d_theta); mix((unsigned long long)(uintptr_t)c.m); mix((unsigned long long)(uintptr_t)c.v);
+    mix((unsigned long long)(uintptr_t)d_x); mix((unsigned long long)(uintptr_t)d_y); mix((unsigned long long)(uintptr_t)d_row_idx);
+    mix((unsigned long long)(uintptr_t)d_losses); mix(c.seed); mix((unsigned long long)G);
+    mix((unsigned long long)(uintptr_t)m->tab_bs); mix((unsigned long long)(uintptr_t)c.c.tab_bc); mix((unsigned long long)(uintptr_t)m->grad2);
+    mix((unsigned long long)c.perturbs); mix((unsigned long long)c.c.perturb); mixf(c.c.lam); mixf(c.c.num_data);
+    for (float v : {c.as.b1, c.as.c1, c.as.b2, c.as.c2, c.as.eps, c.as.decay}) mixf(v);
+    for (float v : {c.bs.b1, c.bs.c1, c.bs.b2, c.bs.c2, c.bs.lam, c.bs.rho, c.bs.gam, c.bs.inv_n}) mixf(v);
+    if (x.ar_key != key) {
+      drop_adam_run_graphs(x);
+      x.ar_key = key;
+    }
+    while (s < n_steps) {
+      // a graph holds steps of ONE batch size: chunks of G inside a stretch of equal batches, one graph for the stretch's
+      // remainder -- so the ragged batch that ends an epoch is a graph of one step, and a run whose epochs do not line up
+      // with its chunks still replays a handful of graphs.  A graph starts on the StepCtl slot it was captured for.
+      int stretch = 1;
+      while (s + stretch < n_steps && h_batch_sizes[s + stretch] == h_batch_sizes[s]) ++stretch;
+      const int len = std::min(G, stretch);
+      const unsigned long long sig = ((unsigned long long)h_batch_sizes[s] << 1) | (unsigned long long)(s & 1);
+      int ci = -1, free_slot = -1, lru = -1;
+      for (int k = 0; k < Extra::AR_GRAPHS; ++k) {
+        if (!x.ar_exec[k]) {
+          if (free_slot < 0) free_slot = k;
+          continue;
+        }
+        if (x.ar_len[k] == len && x.ar_sig[k] == sig) ci = k;
+        if (lru < 0 || x.ar_use[k] < x.ar_use[lru]) lru = k;
+      }
+      if (ci < 0) {
+        ci = free_slot >= 0 ? free_slot : lru;
+        if (x.ar_exec[ci]) {
+          if (x.ar_use[ci] > call_clock) PYZ_HIP(hipStreamSynchronize(st));   // launched by this call: let it finish first
+          (void)hipGraphExecDestroy(x.ar_exec[ci]);
+        }
+        if (x.ar_graph[ci]) (void)hipGraphDestroy(x.ar_graph[ci]);
+        x.ar_exec[ci] = nullptr;
+        x.ar_graph[ci] = nullptr;
+        PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        for (int k = 0; k < len; ++k) step(s + k);
+        hipGraph_t gr = nullptr;
+        PYZ_HIP(hipStreamEndCapture(st, &gr));
+        x.ar_graph[ci] = gr;
+        PYZ_HIP(hipGraphInstantiate(&x.ar_exec[ci], gr, nullptr, nullptr, 0));
+        x.ar_len[ci] = len;
+        x.ar_sig[ci] = sig;
+        ++x.ar_captures;
+      }
+      x.ar_use[ci] = ++x.ar_clock;
+      PYZ_HIP(hipGraphLaunch(x.ar_exec[ci], st));
+      s += len;
+      m->run_graph_steps += len;
+      ++m->run_graph_launches;
+    }
+  }
+  for (; s < n_steps; ++s) {
+    step(s);
+    ++m->run_eager_steps;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_adam_run(pyz_mlp *m, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                 const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr, const int64_t *h_epochs,
+                 int n_steps, double beta_1, double beta_2, float denom_eps, float decay, int perturb, float lam, float num_data,
+                 int64_t step0, int64_t slot0, uint64_t seed, float *d_losses, int use_graph, void *stream) {
+  AdamRunCfg c{};
+  c.bsam = false;
+  c.m = d_m;
+  c.v = d_v;
+  c.as = adam_scalars(0.0f, beta_1, beta_2, 1, denom_eps, decay);   // (lr, bc1, bc2: per step, on the device)
+  c.c.lam = lam;
+  c.c.num_data = num_data;
+  c.perturbs = perturb != 0;
+  c.seed = seed;
+  return adam_run_impl(m, c, d_theta, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, h_epochs, beta_1, beta_2, n_steps, step0, slot0,
+                       d_losses, use_graph, stream);
+}
+
+int pyz_adam_run_info(const pyz_mlp *m, int32_t *h_captures) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (h_captures) *h_captures = static_cast<const pyz_mlp_full *>(m)->x.ar_captures;
+  return PYZ_OK;
+}
+
+int pyz_bsam_run(pyz_mlp *m, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                 const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr, int n_steps, double beta_1,
+                 double beta_2, float lam, float rho, float gam, float num_data, int64_t step0, int64_t slot0, uint64_t seed,
+                 float *d_losses, int use_graph, void *stream) {
+  AdamRunCfg c{};
+  c.bsam = true;
+  c.m = d_m;
+  c.v = d_v;
+  // each scalar in float64, rounded to float32 once (see BsamScal)
+  c.bs.b1 = (float)beta_1;
+  c.bs.c1 = (float)(1.0 - beta_1);
+  c.bs.b2 = (float)beta_2;
+  c.bs.c2 = (float)(1.0 - beta_2);
+  c.bs.lam = lam;
+  c.bs.rho = rho;
+  c.bs.gam = gam;
+  c.bs.inv_n = (float)(1.0 / (double)num_data);
+  c.c.num_data = num_data;
+  c.perturbs = true;
+  c.seed = seed;
+  return adam_run_impl(m, c, d_theta, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, nullptr, beta_1, beta_2, n_steps, step0, slot0,
+                       d_losses, use_graph, stream);
 }
 
 // ---------------------------------------------------------------- H2-H5

@@ -10,6 +10,8 @@
 // i.e. 3 launches for the 2-layer headline model instead of 7.
 #pragma once
 
+#include <type_traits>
+
 #include "pyz_common.h"
 #include "pyz_gemm.h"
 #include "pyz_kernels.h"
@@ -606,6 +608,29 @@ __global__ void k_run_start(StepCtl *ctl, InlineTabs t, int32_t *tab_bs, float *
   pyz_prep_rows(g, g.row_idx + row_off, t.bs[0], (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
 }
 
+// k_run_start with the bias-correction table of a device-resident ADAM / VADAM run (k_set_ctl_tabs_bc)
+__global__ void k_run_start_bc(StepCtl *ctl, InlineTabs t, InlineBc b, int32_t *tab_bs, float *tab_lr, float2 *tab_bc,
+                               long long n, long long row_off, int slot0, PrepArgs g) {
+  if (blockIdx.x == 0) {
+    const int e = threadIdx.x;
+    if (e < t.n) {
+      tab_bs[e] = t.bs[e];
+      tab_lr[e] = t.lr[e];
+      tab_bc[e] = b.bc[e];
+    }
+    if (e == 0) {
+      ctl->batch = t.bs[0];
+      ctl->lr = t.lr[0];
+      ctl->n = n;
+      ctl->row_off = row_off;
+      ctl->i = 0;
+      ctl->slot0 = slot0;
+      ctl->n_run = t.n - 1;
+    }
+  }
+  pyz_prep_rows(g, g.row_idx + row_off, t.bs[0], (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+}
+
 // ---------------------------------------------------------------- all weight gradients + update
 struct WgradLayer {
   const float *in;            // layer input: data x (layer 0) or act[l-1]
@@ -1061,15 +1086,60 @@ struct AdamArgs {
   AdamScal a;
 };
 
-template <int S>
-__global__ void __launch_bounds__(64 * S) k_wgrad_adam(AdamArgs A) {
+// Device-resident runs (pyz_adam_run / pyz_bsam_run): the chained form of the two kernels takes the step's learning rate
+// from StepCtl and ADAM's bias-correction pair from the per-run table at ctl->i, writes the loss at the step's slot,
+// prepares the other StepCtl slot, assembles the next step's batch in its spare workgroups (k_wgrad_all's PrepArgs) and --
+// `perturb`, while step i + 1 exists -- stores the weight with the perturbation of step i + 1 already applied: that
+// perturbation reads only the v and the weight this epilogue holds in registers (VADAM.py:59-65, BSAM.py:63-68), so the
+// run has no perturbation launch after its first step.  The last step of a call stores the unperturbed weight.
+struct RunChain {
+  const float2 *tab_bc;   // ADAM / VADAM: {1 - beta_1^epoch, 1 - beta_2^epoch} per step of the run
+  int perturb;            // 0: the run perturbs in a launch of its own (or not at all: ADAM)
+  float lam, num_data;    // VADAM's perturbation
+};
+
+// duties of the spare workgroup in a chained launch: the loss of step i to loss[stride (slot0 + i) + off], and -- `advance` --
+// the next step's scalars
+__device__ __forceinline__ void pyz_run_duties(const WgradArgs &g, const int l, const int stride, const int off,
+                                               const bool advance) {
+  const double v = pyz_sum_partials(g.part, g.nblk);
+  if (l == 0) {
+    float *lo = g.loss + (long long)stride * (g.ctl->slot0 + g.ctl->i) + off;
+    lo[0] = (float)(v / (double)g.ctl->batch);
+    pyz_note_loss(g.nonfinite, lo[0]);
+    if (advance) pyz_prepare_next(g.ctl, g.next, g.tab_bs, g.tab_lr, g.row_stride);
+  }
+}
+
+// the workgroups past the duties workgroup of a chained launch: the next step's batch (see k_wgrad_all)
+__device__ __forceinline__ void pyz_run_prep(const WgradArgs &g) {
+  if (blockIdx.x > (unsigned)g.tiles && g.prep.src) {
+    const int i2 = g.ctl->i + 1;
+    if (i2 < g.ctl->n_run)
+      pyz_prep_rows(g.prep, g.prep.row_idx + g.ctl->row_off + g.prep.row_stride, g.prep.tab_bs[i2],
+                    (int)blockIdx.x - g.tiles - 1, (int)gridDim.x - g.tiles - 1, (int)blockIdx.x);
+  }
+}
+
+struct AdamRunArgs : AdamArgs {
+  RunChain c;
+};
+
+// CHAIN: the chained form (AdamRunArgs); the eager instantiations k_wgrad_adam<S> contain none of it
+template <int S, bool CHAIN = false>
+__global__ void __launch_bounds__(64 * S) k_wgrad_adam(std::conditional_t<CHAIN, AdamRunArgs, AdamArgs> A) {
   extern __shared__ float red[];
   const WgradArgs &g = A.w;
   constexpr int EPT = 16 / S;  // tile elements per thread in the epilogue
   const int w = pyz_wave_id(), l = threadIdx.x & 63;
   const int r = l & 31, h = l >> 5;
   if (blockIdx.x >= (unsigned)g.tiles) {  // the duties workgroup: the step's loss and the non-finite count
-    if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    if constexpr (CHAIN) {
+      if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_run_duties(g, l, 1, 0, true);
+      pyz_run_prep(g);
+    } else {
+      if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    }
     return;
   }
   const int tile = pyz_xcd_remap(blockIdx.x, g.tiles);
@@ -1087,6 +1157,18 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_adam(AdamArgs A) {
   long long ee[EPT];
   bool ev[EPT];
   float th0[EPT], m0[EPT], v0[EPT];
+  float zn[CHAIN ? EPT : 1];   // chained, perturbing: the next step's eps
+  AdamScal sc;                 // chained: the update's scalars with this step's lr, bc1, bc2
+  bool perturb_next = false;
+  if constexpr (CHAIN) {
+    const int si = g.ctl->i;
+    const float2 bc = A.c.tab_bc[si];
+    sc = A.a;
+    sc.lr = g.ctl->lr;
+    sc.bc1 = bc.x;
+    sc.bc2 = bc.y;
+    perturb_next = A.c.perturb && si + 1 < g.ctl->n_run;
+  }
   auto prefetch = [&]() {
 #pragma unroll
     for (int q = 0; q < EPT; ++q) {
@@ -1105,6 +1187,13 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_adam(AdamArgs A) {
       th0[q] = g.theta[ee[q]];
       m0[q] = A.m[ee[q]];
       v0[q] = A.v[ee[q]];
+    }
+    if constexpr (CHAIN) {
+      if (perturb_next) {
+        const uint32_t n1 = (uint32_t)(g.ctl->n + 1);
+#pragma unroll
+        for (int q = 0; q < EPT; ++q) zn[q] = pyz_normal1(g.seed, PYZ_STREAM_VADAM, n1, (uint64_t)ee[q]);
+      }
     }
   };
 
@@ -1179,12 +1268,21 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_adam(AdamArgs A) {
 #pragma unroll
   for (int q = 0; q < EPT; ++q) {
     if (!ev[q]) continue;
-    const PyzAdamOut o = pyz_adam_math(A.a, th0[q], m0[q], v0[q], gv[q], sv[q] / fb);
-    pyz_st(g.theta + ee[q], o.th, g.wt);
-    pyz_st(A.m + ee[q], o.m, g.wt);
-    pyz_st(A.v + ee[q], o.v, g.wt);
+    if constexpr (CHAIN) {
+      const PyzAdamOut o = pyz_adam_math_pinned(sc, th0[q], m0[q], v0[q], gv[q], sv[q] / fb);
+      const float th = perturb_next ? pyz_vadam_perturb_math(A.c.num_data, A.c.lam, o.th, o.v, zn[q]) : o.th;
+      pyz_st(g.theta + ee[q], th, g.wt);
+      pyz_st(A.m + ee[q], o.m, g.wt);
+      pyz_st(A.v + ee[q], o.v, g.wt);
+    } else {
+      const PyzAdamOut o = pyz_adam_math(A.a, th0[q], m0[q], v0[q], gv[q], sv[q] / fb);
+      pyz_st(g.theta + ee[q], o.th, g.wt);
+      pyz_st(A.m + ee[q], o.m, g.wt);
+      pyz_st(A.v + ee[q], o.v, g.wt);
+    }
   }
 }
+
 
 // ---------------------------------------------------------------- BSAM: gradients + ascent, gradients + update
 // BSAM.step (BSAM.py:46-119) takes two gradient passes on one batch.  After the first the weights ascend along g1 / v
@@ -1202,15 +1300,25 @@ struct BsamArgs {
   BsamScal a;
 };
 
-template <int S, int PHASE>
-__global__ void __launch_bounds__(64 * S) k_wgrad_bsam(BsamArgs A) {
+struct BsamRunArgs : BsamArgs {
+  RunChain c;
+};
+
+// CHAIN: the chained form (BsamRunArgs); the eager instantiations k_wgrad_bsam<S, PHASE> contain none of it
+template <int S, int PHASE, bool CHAIN = false>
+__global__ void __launch_bounds__(64 * S) k_wgrad_bsam(std::conditional_t<CHAIN, BsamRunArgs, BsamArgs> A) {
   extern __shared__ float red[];
   const WgradArgs &g = A.w;
   constexpr int EPT = 16 / S;  // tile elements per thread in the epilogue
   const int w = pyz_wave_id(), l = threadIdx.x & 63;
   const int r = l & 31, h = l >> 5;
   if (blockIdx.x >= (unsigned)g.tiles) {  // the duties workgroup: the pass's loss and the non-finite count
-    if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    if constexpr (CHAIN) {   // {l1, l2} of step i at 2 (slot0 + i); only the second pass advances the StepCtl
+      if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_run_duties(g, l, 2, PHASE, PHASE == 1);
+      if constexpr (PHASE == 1) pyz_run_prep(g);
+    } else {
+      if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    }
     return;
   }
   const int tile = pyz_xcd_remap(blockIdx.x, g.tiles);
@@ -1228,6 +1336,14 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_bsam(BsamArgs A) {
   long long ee[EPT];
   bool ev[EPT];
   float th0[EPT], v0[EPT], m0[PHASE ? EPT : 1], g10[PHASE ? EPT : 1];
+  float zn[(CHAIN && PHASE) ? EPT : 1];   // chained second pass, perturbing: the next step's eps
+  BsamScal sc;                            // chained: the step's scalars with its lr
+  bool perturb_next = false;
+  if constexpr (CHAIN) {
+    sc = A.a;
+    sc.lr = g.ctl->lr;
+    if constexpr (PHASE == 1) perturb_next = A.c.perturb && g.ctl->i + 1 < g.ctl->n_run;
+  }
   auto prefetch = [&]() {
 #pragma unroll
     for (int q = 0; q < EPT; ++q) {
@@ -1248,6 +1364,13 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_bsam(BsamArgs A) {
       if constexpr (PHASE == 1) {
         m0[q] = A.m[ee[q]];
         g10[q] = A.g1[ee[q]];
+      }
+    }
+    if constexpr (CHAIN && PHASE == 1) {
+      if (perturb_next) {
+        const uint32_t n1 = (uint32_t)(g.ctl->n + 1);
+#pragma unroll
+        for (int q = 0; q < EPT; ++q) zn[q] = pyz_normal1(g.seed, PYZ_STREAM_BSAM, n1, (uint64_t)ee[q]);
       }
     }
   };
@@ -1307,7 +1430,13 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_bsam(BsamArgs A) {
     if (!ev[q]) continue;
     if constexpr (PHASE == 0) {
       pyz_st(A.g1 + ee[q], gv[q], g.wt);
-      pyz_st(g.theta + ee[q], pyz_bsam_ascent_math(A.a, th0[q], v0[q], gv[q]), g.wt);
+      pyz_st(g.theta + ee[q], pyz_bsam_ascent_math(A.a, th0[q], v0[q], gv[q]), g.wt);   // (rho: lr plays no part)
+    } else if constexpr (CHAIN) {
+      const PyzBsamOut o = pyz_bsam_math(sc, th0[q], m0[q], v0[q], gv[q], g10[q]);
+      const float th = perturb_next ? pyz_bsam_perturb_math(sc.inv_n, o.th, o.v, zn[q]) : o.th;
+      pyz_st(g.theta + ee[q], th, g.wt);
+      pyz_st(A.m + ee[q], o.m, g.wt);
+      pyz_st(A.v + ee[q], o.v, g.wt);
     } else {
       const PyzBsamOut o = pyz_bsam_math(A.a, th0[q], m0[q], v0[q], gv[q], g10[q]);
       pyz_st(g.theta + ee[q], o.th, g.wt);

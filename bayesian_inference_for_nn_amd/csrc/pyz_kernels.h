@@ -97,6 +97,30 @@ __global__ void k_set_ctl_tabs(StepCtl *ctl, InlineTabs t, int32_t *tab_bs, floa
   }
 }
 
+// Device-resident ADAM / VADAM runs (pyz_adam_run) carry a third table beside tab_bs / tab_lr: the bias-correction pair
+// {1 - beta_1^epoch, 1 - beta_2^epoch} of every step (the host knows where the epochs begin).  Short runs: inline as well.
+struct InlineBc {
+  float2 bc[PYZ_INLINE_TAB + 1];
+};
+__global__ void k_set_ctl_tabs_bc(StepCtl *ctl, InlineTabs t, InlineBc b, int32_t *tab_bs, float *tab_lr, float2 *tab_bc,
+                                  long long n, long long row_off, int slot0) {
+  const int e = threadIdx.x;
+  if (e < t.n) {
+    tab_bs[e] = t.bs[e];
+    tab_lr[e] = t.lr[e];
+    tab_bc[e] = b.bc[e];
+  }
+  if (e == 0) {
+    ctl->batch = t.bs[0];
+    ctl->lr = t.lr[0];
+    ctl->n = n;
+    ctl->row_off = row_off;
+    ctl->i = 0;
+    ctl->slot0 = slot0;
+    ctl->n_run = t.n - 1;
+  }
+}
+
 // The last kernel of a step prepares the OTHER StepCtl slot for the next step
 // (ping-pong: nobody reads that slot during this step).
 __device__ __forceinline__ void pyz_prepare_next(const StepCtl *ctl, StepCtl *next, const int32_t *tab_bs,
@@ -269,6 +293,28 @@ __device__ __forceinline__ PyzAdamOut pyz_adam_math(const AdamScal &a, const flo
   return o;
 }
 
+// pyz_adam_math with its contractions spelled out.  In `b1 m0 + c1 (g + decay w)` and `b2 v0 + c2 s` the compiler is free to
+// fuse either product into the sum, and the two choices round differently once m0 / v0 are not zero.  The eager
+// k_wgrad_adam<S> (scalar code) fuses the FIRST product -- fma(b1, m0, c1 t), fma(b2, v0, c2 s), t = fma(decay, w, g) --
+// while the chained form, whose longer epilogue the compiler vectorises in pairs, came out with the other one: one unit in
+// the last place per step against the eager steps.  The chained form therefore states the eager kernel's choice; with it
+// pyz_adam_run equals pyz_adam_step bit for bit (tests/test_gpu_adam_bsam_run.py, every S).  This copy follows the ISA of
+// the eager kernel, not the other way round: after a compiler change that makes those tests fail, read the fused
+// multiply-adds off the disassembly of k_wgrad_adam<S> again and restate them here.  The chained BSAM epilogue carries no
+// such copy -- the compiler contracts pyz_bsam_math alike in both forms today, and the same tests watch that too.
+__device__ __forceinline__ PyzAdamOut pyz_adam_math_pinned(const AdamScal &a, const float w, const float m0, const float v0,
+                                                           const float g, const float s) {
+  PyzAdamOut o;
+  const float t = __builtin_fmaf(a.decay, w, g);
+  const float ct = a.c1 * t, cs = a.c2 * s;
+  o.m = __builtin_fmaf(a.b1, m0, ct);
+  o.v = __builtin_fmaf(a.b2, v0, cs);
+  const float mh = o.m / a.bc1, vh = o.v / a.bc2;
+  const float num = a.lr * mh, den = sqrtf(vh) + a.eps;
+  o.th = w - num / den;
+  return o;
+}
+
 // ADAM / VADAM update for nets the fused path does not take: g and s come from the weight-gradient kernels
 // (k_dense_bwd_weight_sq); the first wave also finalises the batch loss.
 __global__ void k_adam_update(float *theta, float *m, float *v, const float *g, const float *s, long long D, AdamScal a,
@@ -292,8 +338,14 @@ __global__ void k_adam_update(float *theta, float *m, float *v, const float *g, 
 // VADAM.step's weight perturbation (VADAM.py:59-65): w += eps / sqrt(N (v + lam)), eps ~ N(0, 1) from the Philox stream
 // (seed, PYZ_STREAM_VADAM, step) or injected.  Not undone after the step: the weights random-walk, as in the reference.
 // Each thread owns four consecutive elements (one Philox call).
-__global__ void k_vadam_perturb(float *theta, const float *v, long long D, float lam, float num_data, uint64_t seed,
-                                uint32_t step, const float *eps) {
+// VADAM.py:59-65 for one element (k_vadam_perturb, and the chained k_wgrad_adam, whose epilogue perturbs for the next step)
+__device__ __forceinline__ float pyz_vadam_perturb_math(const float num_data, const float lam, const float w, const float v,
+                                                        const float eps) {
+  return w + eps * (1.0f / sqrtf(num_data * (v + lam)));
+}
+
+__device__ __forceinline__ void pyz_vadam_perturb_elems(float *theta, const float *v, long long D, float lam, float num_data,
+                                                        uint64_t seed, uint32_t step, const float *eps) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long e0 = 4 * t;
   if (e0 >= D) return;
@@ -308,8 +360,19 @@ __global__ void k_vadam_perturb(float *theta, const float *v, long long D, float
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const long long e = e0 + j;
-    if (e < D) theta[e] += z[j] * (1.0f / sqrtf(num_data * (v[e] + lam)));
+    if (e < D) theta[e] = pyz_vadam_perturb_math(num_data, lam, theta[e], v[e], z[j]);
   }
+}
+
+__global__ void k_vadam_perturb(float *theta, const float *v, long long D, float lam, float num_data, uint64_t seed,
+                                uint32_t step, const float *eps) {
+  pyz_vadam_perturb_elems(theta, v, D, lam, num_data, seed, step, eps);
+}
+
+// inside a device-resident run (PYZ_ADAM_FUSE_PERTURB=0): the Philox step is the StepCtl's count
+__global__ void k_vadam_perturb_run(float *theta, const float *v, long long D, float lam, float num_data, uint64_t seed,
+                                    const StepCtl *ctl) {
+  pyz_vadam_perturb_elems(theta, v, D, lam, num_data, seed, (uint32_t)ctl->n, nullptr);
 }
 
 // ---------------------------------------------------------------- BSAM
@@ -358,8 +421,8 @@ __device__ __forceinline__ void pyz_bsam_loss(const StepCtl *ctl, const double *
 
 // BSAM.step's weight perturbation: eps ~ N(0, 1) from the Philox stream (seed, PYZ_STREAM_BSAM, step) or injected.  Not
 // undone after the step, as in the reference.  Each thread owns four consecutive elements (one Philox call).
-__global__ void k_bsam_perturb(float *theta, const float *v, long long D, float inv_n, uint64_t seed, uint32_t step,
-                               const float *eps) {
+__device__ __forceinline__ void pyz_bsam_perturb_elems(float *theta, const float *v, long long D, float inv_n, uint64_t seed,
+                                                       uint32_t step, const float *eps) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long e0 = 4 * t;
   if (e0 >= D) return;
@@ -376,6 +439,16 @@ __global__ void k_bsam_perturb(float *theta, const float *v, long long D, float 
     const long long e = e0 + j;
     if (e < D) theta[e] = pyz_bsam_perturb_math(inv_n, theta[e], v[e], z[j]);
   }
+}
+
+__global__ void k_bsam_perturb(float *theta, const float *v, long long D, float inv_n, uint64_t seed, uint32_t step,
+                               const float *eps) {
+  pyz_bsam_perturb_elems(theta, v, D, inv_n, seed, step, eps);
+}
+
+// inside a device-resident run (PYZ_ADAM_FUSE_PERTURB=0): the Philox step is the StepCtl's count
+__global__ void k_bsam_perturb_run(float *theta, const float *v, long long D, float inv_n, uint64_t seed, const StepCtl *ctl) {
+  pyz_bsam_perturb_elems(theta, v, D, inv_n, seed, (uint32_t)ctl->n, nullptr);
 }
 
 // BSAM for nets the fused path does not take, after the first pass: g (from the weight-gradient kernels) is kept in g1

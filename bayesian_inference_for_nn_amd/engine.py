@@ -271,7 +271,7 @@ class MLPPlan:
                                     1 if use_graph else 0, _stream()))
 
     def last_run_path(self):
-        """("graph" | "eager" | "mixed", steps) of the last sgld_run / sgd_run / swag_run call on this plan."""
+        """("graph" | "eager" | "mixed", steps) of the last sgld_run / sgd_run / swag_run / adam_run / bsam_run call on this plan."""
         g, e, n = C.c_int32(), C.c_int32(), C.c_int32()
         check(self.lib.pyz_last_run_info(self.h, C.byref(g), C.byref(e), C.byref(n)))
         kind = "graph" if e.value == 0 else ("eager" if g.value == 0 else "mixed")
@@ -337,6 +337,55 @@ class MLPPlan:
                                    float(prior_mean), float(prior_rho), ptr(prior_mean_vec), ptr(prior_rho_vec), int(step0),
                                    int(slot0), int(seed), ptr(costs_out), val_plan.h if val_plan is not None else None,
                                    ptr(val_x), ptr(val_y), n_val, ptr(val_losses_out), 1 if use_graph else 0, _stream()))
+
+    def _run_tables(self, row_idx, batch_sizes, lrs, losses_out, slot0, per_step=1):
+        """The argument checks the chained runs share (see sgd_run); returns the host tables as ctypes arrays."""
+        n_steps = len(batch_sizes)
+        assert len(lrs) == n_steps and n_steps > 0
+        _f32(losses_out, name="losses_out")
+        if (slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch
+                or losses_out.numel() < per_step * (slot0 + n_steps)):
+            raise ValueError("row_idx / losses_out too small")
+        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
+            raise ValueError("batch size outside the plan")
+        return (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes]), (C.c_float * n_steps)(*[float(v) for v in lrs])
+
+    def adam_run(self, theta, m, v, x, y, row_idx, batch_sizes, lrs, epochs, beta_1, beta_2, losses_out, denom_eps=1e-3,
+                 decay=0.0, perturb=False, lam=0.0, num_data=1.0, step0=0, seed=0, use_graph=True, slot0=0):
+        """n = len(batch_sizes) ADAM steps (perturb: VADAM steps, each behind its weight perturbation) without host work in
+        between (see sgld_run for the table layout).  epochs[s] >= 1: the epoch count of step s's bias correction; step s
+        is optimizer step step0 + s (VADAM's Philox step) and writes its loss to losses_out[slot0 + s]."""
+        for t, nm in ((theta, "theta"), (m, "m"), (v, "v")):
+            _f32(t, (self.D,), nm)
+        self._check_xy(x, y, row_idx, 1)
+        bs, lr = self._run_tables(row_idx, batch_sizes, lrs, losses_out, slot0)
+        n_steps = len(batch_sizes)
+        if len(epochs) != n_steps:
+            raise ValueError("one epoch count per step")
+        ep = (C.c_int64 * n_steps)(*[int(e) for e in epochs])
+        check(self.lib.pyz_adam_run(self.h, ptr(theta), ptr(m), ptr(v), ptr(x), ptr(y), ptr(row_idx), bs, lr, ep, n_steps,
+                                    float(beta_1), float(beta_2), float(denom_eps), float(decay), 1 if perturb else 0,
+                                    float(lam), float(num_data), int(step0), int(slot0), int(seed), ptr(losses_out),
+                                    1 if use_graph else 0, _stream()))
+
+    def bsam_run(self, theta, m, v, x, y, row_idx, batch_sizes, lrs, beta_1, beta_2, lam, rho, gam, num_data, step0, seed,
+                 losses_out, use_graph=True, slot0=0):
+        """n = len(batch_sizes) BSAM steps without host work in between; step s is optimizer step step0 + s (its Philox
+        step) and writes l1, l2 to losses_out[2 (slot0 + s) ..]."""
+        for t, nm in ((theta, "theta"), (m, "m"), (v, "v")):
+            _f32(t, (self.D,), nm)
+        self._check_xy(x, y, row_idx, 1)
+        bs, lr = self._run_tables(row_idx, batch_sizes, lrs, losses_out, slot0, per_step=2)
+        check(self.lib.pyz_bsam_run(self.h, ptr(theta), ptr(m), ptr(v), ptr(x), ptr(y), ptr(row_idx), bs, lr,
+                                    len(batch_sizes), float(beta_1), float(beta_2), float(lam), float(rho), float(gam),
+                                    float(num_data), int(step0), int(slot0), int(seed), ptr(losses_out),
+                                    1 if use_graph else 0, _stream()))
+
+    def adam_run_captures(self) -> int:
+        """Graphs the last adam_run / bsam_run call on this plan had to capture (0: every stretch was replayed)."""
+        n = C.c_int32()
+        check(self.lib.pyz_adam_run_info(self.h, C.byref(n)))
+        return n.value
 
     # ------------------------------------------------------------------ H2-H5
     def hmc_step(self, q, x, y, L, epsilon, m, prior_mean, prior_sigma, uniforms, step, seed, stats_out, burning=False,

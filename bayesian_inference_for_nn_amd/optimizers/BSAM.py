@@ -7,6 +7,7 @@ with the quirks kept as written: the square root of the already scaled v, the FI
 lam and gam added as scalars, no bias correction and no square root in the step's denominator.  m starts at 0 and v at 1
 (BSAM.py:121-141).  Hyperparameters: lr, beta_1, beta_2, batch_size, lam, rho, gam (all read unconditionally,
 BSAM.py:150-164); kwarg starting_model.  The returned loss is the epoch's running sum of l1 + l2 over the batches seen.
+A quiet train() runs as device-resident runs (pyz_bsam_run, see _AdamFamily._train_resident).
 One device step is seven launches on the fused path: the perturbation, and for each pass the forward, the head and a
 weight-gradient kernel whose epilogue applies the ascent (first pass) or the update (second pass).
 
@@ -61,6 +62,19 @@ class BSAM(_AdamFamily):
                 losses_file.write(str(l2))
         self._n += 1
         return DeviceScalar(self._running_dev.clone(), 0, 1.0 / self._seen_batches)
+
+    _losses_per_step = 2                                       # l1, l2
+
+    def _run_losses(self, n_steps):
+        import torch
+        if getattr(self, "_res_losses2", None) is None or self._res_losses2.numel() < 2 * self._res_cap:
+            self._res_losses2 = torch.zeros(2 * self._res_cap, device="cuda")
+        return self._res_losses2
+
+    def _launch_run(self, row_idx, losses, sizes, lrs, epochs, s0):
+        self._plan.bsam_run(self._theta, self._m_dev, self._v_dev, self._x_dev, self._y_dev, row_idx, sizes, lrs,
+                            self._beta_1, self._beta_2, self._lam, self._rho, self._gam, self._num_data, self._n + s0,
+                            self._seed, losses, slot0=s0)
 
     def result(self) -> BayesianModel:
         """Normal(loc = w, scale = 1 / (N v)) per Dense layer (BSAM.py:167-182)."""

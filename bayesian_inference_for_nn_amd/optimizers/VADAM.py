@@ -33,6 +33,12 @@ class VADAM(_AdamFamily):
         perturb = lambda: self._plan.vadam_perturb(self._theta, self._v_dev, self._lam, self._num_data, self._n, self._seed)
         return self._adam_step(save_document_path, lam_n, lam_n, perturb)
 
+    def _launch_run(self, row_idx, losses, sizes, lrs, epochs, s0):
+        lam_n = float(self._lam) / self._num_data
+        self._plan.adam_run(self._theta, self._m_dev, self._v_dev, self._x_dev, self._y_dev, row_idx, sizes, lrs, epochs,
+                            self._beta_1, self._beta_2, losses, denom_eps=lam_n, decay=lam_n, perturb=True, lam=self._lam,
+                            num_data=self._num_data, step0=self._n + s0, seed=self._seed, slot0=s0)
+
     def result(self) -> BayesianModel:
         """Normal(loc = w, scale = v) per Dense layer (VADAM.py:153-172).  As in the reference the scale is the raw
         second-moment vector v, not a standard deviation derived from it."""

@@ -236,6 +236,42 @@ int pyz_bbb_run(pyz_mlp *mlp, float *d_mu, float *d_rho, float *d_w, const float
                 pyz_mlp *val_plan, const float *d_val_x, const void *d_val_y, int n_val,
                 float *d_val_losses, int use_graph, void *stream);
 
+/* The ADAM / VADAM train loop (ADAM.step / VADAM.step inside Optimizer.train, ADAM.py:42-86, VADAM.py:45-99,
+ * Optimizer.py:121-134) as ONE device-resident run of n_steps steps, replayed from captured hipGraphs like pyz_sgld_run:
+ * d_row_idx (slots, max_batch) / h_batch_sizes / h_lr / slot0 as there.  h_epochs[s] (>= 1) is the epoch count step s uses
+ * for its bias correction (the host knows where epochs begin); 1 - beta^epoch is evaluated per step as pyz_adam_step does
+ * (float64, rounded to float32 once) and kept in a device table beside the learning rates.  Step i of the call is
+ * optimizer step step0 + i and writes its batch loss to d_losses[slot0 + i].  perturb != 0 selects VADAM: the perturbation
+ * of pyz_vadam_perturb (Philox stream 5, step step0 + i, no injected noise; lam, num_data > 0) runs before each step's
+ * gradients -- for the first step of the call as a launch, for every later one in the epilogue of the weight-gradient
+ * kernel of the step before it, which holds the v and the weight it reads (PYZ_ADAM_FUSE_PERTURB=0, read once: a launch
+ * per step).  The last step of a call leaves the weights unperturbed.  Every step is launched for its own batch size, so
+ * a graph holds steps of one batch size (chunks of PYZ_GRAPH_STEPS inside a stretch of equal batches, one graph for the
+ * stretch's remainder; 32 graphs by length, batch size and starting slot, least recently used one replaced).
+ * Needs the fused step (last layer of at most 32 units), else PYZ_E_INVALID; every refusal returns before anything is
+ * enqueued.  d_theta, d_m, d_v and every loss equal n_steps calls of pyz_adam_step (with pyz_vadam_perturb before each
+ * when perturb) bit for bit, on ragged batches and across epoch changes, with use_graph on or off.  pyz_last_run_info
+ * reports the split; while a probe is open the run launches eagerly. */
+int pyz_adam_run(pyz_mlp *mlp, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                 const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
+                 const int64_t *h_epochs, int n_steps, double beta_1, double beta_2, float denom_eps,
+                 float decay, int perturb, float lam, float num_data, int64_t step0, int64_t slot0,
+                 uint64_t seed, float *d_losses, int use_graph, void *stream);
+
+/* The BSAM train loop (BSAM.step inside Optimizer.train, BSAM.py:46-119, Optimizer.py:121-134) as ONE device-resident
+ * run, as pyz_adam_run: step i of the call is optimizer step step0 + i (its Philox step, stream 6) and writes {l1, l2} to
+ * d_losses[2 (slot0 + i) ..].  Both passes of a step run on one StepCtl slot; the second pass's weight-gradient kernel
+ * advances it and -- unless PYZ_ADAM_FUSE_PERTURB=0 -- stores the weights with the perturbation of step i + 1 applied.
+ * Results equal n_steps calls of pyz_bsam_step bit for bit. */
+int pyz_bsam_run(pyz_mlp *mlp, float *d_theta, float *d_m, float *d_v, const float *d_x, const void *d_y,
+                 const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr, int n_steps,
+                 double beta_1, double beta_2, float lam, float rho, float gam, float num_data,
+                 int64_t step0, int64_t slot0, uint64_t seed, float *d_losses, int use_graph, void *stream);
+
+/* *h_captures = the graphs the last pyz_adam_run / pyz_bsam_run on the plan had to capture (0: every stretch was
+ * replayed from the cache). */
+int pyz_adam_run_info(const pyz_mlp *mlp, int32_t *h_captures);
+
 /* ---- H2-H5: one HMC proposal (HMC.py:74-104) for P independent chains on the
  * full training split (d_x, d_y, n_rows).  d_q (P, D) is updated in place when
  * accepted.  Momentum p = m * z with z from Philox (seed, step, chain) or

@@ -7,7 +7,11 @@ the same batch table through its eager per-step entry point:
     vadam  pyz_vadam_perturb + pyz_adam_step   (Philox noise)
 us_per_step: device events around `--steps` steps (host enqueue included), median of `--rounds` rounds with the
 variants alternating inside each round.  kernel_us_per_step: the sum of the kernels' own durations per step
-(KernelProbe) over 16 steps, and `kernels` the split by kernel.  Prints one JSON line."""
+(KernelProbe) over 16 steps, and `kernels` the split by kernel.
+resident: the same steps as device-resident runs (tools/resident_legs.py), in us per step, every leg once per round in turn
+-- `eager` (the loop above, measured again beside the others), `run` (the bare C-ABI run), `run_unfused`
+(PYZ_ADAM_FUSE_PERTURB=0, a child process), `train_run` (a quiet train() through the run) and `train_loop` (the same call
+with PYZ_ADAM_RUN=0); `resident_rounds` keeps every round.  Prints one JSON line."""
 
 import argparse
 import json
@@ -21,6 +25,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from bayesian_inference_for_nn_amd import engine, synth  # noqa: E402
+
+import resident_legs  # noqa: E402  (tools/ is the script's directory)
 
 DIMS, ACTS = (784, 200, 10), ("relu", "softmax")
 BATCH, N_ROWS = 1024, 7 * 1024 + 896
@@ -77,6 +83,18 @@ def main():
             e1.synchronize()
             times[k].append(e0.elapsed_time(e1) * 1e3 / args.steps)
     us = {k: float(np.median(v)) for k, v in times.items()}
+
+    def eager_round(k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for s in range(args.steps):
+            step(k, s)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.steps
+
+    res_kinds = ("adam", "vadam")
+    res_times = resident_legs.measure(res_kinds, args.steps, 1, args.rounds, {k: (lambda k=k: eager_round(k)) for k in res_kinds})
     kernel_us, split = {}, {}
     for k in kinds:
         with engine.KernelProbe(256) as kp:
@@ -90,7 +108,8 @@ def main():
                       "us_per_step_rounds": {k: [round(t, 2) for t in v] for k, v in times.items()},
                       "ratio_adam_sgd": round(us["adam"] / us["sgd"], 3), "ratio_vadam_sgd": round(us["vadam"] / us["sgd"], 3),
                       "kernel_us_per_step": {k: round(v, 2) for k, v in kernel_us.items()},
-                      "kernel_ratio_adam_sgd": round(kernel_us["adam"] / kernel_us["sgd"], 3), "kernels": split}))
+                      "kernel_ratio_adam_sgd": round(kernel_us["adam"] / kernel_us["sgd"], 3), "kernels": split,
+                      "resident": resident_legs.summary(res_times), "resident_rounds": res_times}))
 
 
 if __name__ == "__main__":
