@@ -11,6 +11,7 @@
 #include "pyz_gemm_ring.h"
 #include "pyz_hmc_fused.h"
 #include "pyz_hmc_multi.h"
+#include "pyz_input_grad.h"
 #include "pyz_kernels.h"
 #include "pyz_rng.h"
 
@@ -637,6 +638,41 @@ AdamScal adam_scalars(float lr, double beta_1, double beta_2, long long epoch, f
   a.eps = denom_eps;
   a.decay = decay;
   return a;
+}
+
+// delta[0] of every draw of a chunk (pyz_input_grad): forward, head / loss, and the data gradients down to layer 1 -- the
+// sequences of launch_loss_backward without their weight-gradient launches
+void launch_delta0(pyz_mlp *m, const float *theta, int P, const float *x, const void *y, int n, hipStream_t st) {
+  if (can_fuse(m)) {
+    launch_forward(m, theta, m->D, P, x, nullptr, n, m->ctl, st, nullptr, m->L - 1);   // hidden layers
+    launch_head(m, theta, m->D, P, x, y, nullptr, n, m->ctl, true, st);                // leaves delta[L-1] and delta[L-2]
+    launch_bwd_data_hidden(m, theta, m->D, P, n, m->ctl, st);
+    return;
+  }
+  launch_forward(m, theta, m->D, P, x, nullptr, n, m->ctl, st);
+  launch_loss(m, P, y, nullptr, n, m->ctl, true, st);
+  m->cur_nblk = loss_nblk(m, n);
+  if (m->L > 1) {   // delta[L-2] = (delta[L-1] W_{L-1}^T) * act'(h_{L-2}): the layer launch_bwd_data_hidden leaves to the head
+    const int l = m->L - 1, K = m->dims[l], N = m->dims[l + 1];
+    DenseArgs g{};
+    g.K = K;
+    g.N = N;
+    g.in = m->delta[l];
+    g.in_pstride = (long long)m->max_batch * N;
+    g.lda = N;
+    g.theta = theta;
+    g.theta_pstride = m->D;
+    g.w_off = m->w_off[l];
+    g.out = m->delta[l - 1];
+    g.out_pstride = (long long)m->max_batch * K;
+    g.aux = m->act[l - 1];
+    g.aux_pstride = (long long)m->max_batch * K;
+    g.act = m->acts[l - 1];
+    g.vec = (N % 8 == 0) && (m->w_off[l] % 4 == 0) && (P == 1 || m->D % 4 == 0) && aligned16(theta) ? 1 : 0;
+    g.ctl = m->ctl;
+    pyz_launch_bwd_data(g, n, P, st);
+  }
+  launch_bwd_data_hidden(m, theta, m->D, P, n, m->ctl, st);
 }
 
 }  // namespace
@@ -2662,6 +2698,51 @@ int pyz_predict(pyz_mlp *m, const float *d_weights, int n_samples, const float *
                softmax, n, d_samples ? d_samples + (long long)s0 * n * C : nullptr);
     PYZ_LAUNCH(k_predict_mean, dim3((unsigned)cdiv((long long)n * C, 256)), dim3(256), 0, st, m->act[m->L - 1],
                (long long)m->max_batch * C, (long long)n * C, S, d_mean, s0 > 0 ? 1 : 0, 1.0f / (float)n_samples);
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- R2
+int pyz_input_grad(pyz_mlp *m, const float *d_weights, int n_samples, const float *d_x, const void *d_y, int n, float scale,
+                   float *d_xgrad, float epsilon, float *d_xadv, float *d_loss, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_samples < 1 || n < 1) return pyz_fail(PYZ_E_INVALID, "n_samples and n must be positive");
+  if (n > m->max_batch) return pyz_fail(PYZ_E_SHAPE, "n %d exceeds the plan's max_batch %d", n, m->max_batch);
+  int rc = check_loss_combo(m);
+  if (rc) return rc;
+  if (!d_weights || !d_x || !d_y || !d_xgrad) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st))) return rc;
+  m->grad_owner = 2;   // (the losses of a call without d_loss land in m->scal)
+  const int N = m->dims[1];
+  const int chunk = std::min(m->max_p, pyz_input_grad_max_draws(N));
+  for (int s0 = 0; s0 < n_samples; s0 += chunk) {
+    const int P = std::min(chunk, n_samples - s0);
+    const float *theta = d_weights + (long long)s0 * m->D;
+    launch_delta0(m, theta, P, d_x, d_y, n, st);
+    PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, m->ctl, d_loss ? d_loss + s0 : m->scal,
+               m->nonfinite);
+    InputGradArgs g{};
+    g.delta = m->delta[0];
+    g.delta_pstride = (long long)m->max_batch * N;
+    g.theta = theta;
+    g.theta_pstride = m->D;
+    g.w_off = m->w_off[0];
+    g.K = m->dims[0];
+    g.N = N;
+    g.P = P;
+    g.rows = n;
+    g.vec = (N % 8 == 0) && (m->w_off[0] % 4 == 0) && (P == 1 || m->D % 4 == 0) && aligned16(theta) ? 1 : 0;
+    g.scale = scale;
+    g.out = d_xgrad;
+    g.accumulate = s0 > 0 ? 1 : 0;
+    if (d_xadv && s0 + P >= n_samples) {   // the last chunk: G is complete in its epilogue
+      g.x = d_x;
+      g.xadv = d_xadv;
+      g.eps = epsilon;
+    }
+    pyz_launch_input_grad(g, st);
   }
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;

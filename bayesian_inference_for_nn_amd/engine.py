@@ -544,6 +544,27 @@ class MLPPlan:
         check(self.lib.pyz_predict(self.h, ptr(weights), S, ptr(x), n, ptr(samples), ptr(mean), _stream()))
         return samples, mean
 
+    # ------------------------------------------------------------------ R2
+    def input_grad(self, weights, x, y, scale=1.0, epsilon=None):
+        """(xgrad, xadv or None, losses): xgrad (n, in) = scale * sum over the draws `weights` (S, D) of the gradient of
+        each draw's mean loss over the n rows of x with respect to x; with epsilon, xadv = x + epsilon * sign(xgrad)
+        (Robustness.py:115-144); losses (S,) = each draw's mean loss."""
+        _f32(weights, name="weights")
+        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
+            raise ValueError(f"weights must be (draws >= 1, {self.D})")
+        S = int(weights.shape[0])
+        _f32(x, name="x")
+        n = int(x.shape[0]) if x.dim() == 2 else 0
+        self._check_xy(x, y, None, n)
+        if y is None:
+            raise TypeError("y is required")
+        xgrad = torch.empty_like(x)
+        xadv = torch.empty_like(x) if epsilon is not None else None
+        losses = torch.empty((S,), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_input_grad(self.h, ptr(weights), S, ptr(x), ptr(y), n, float(scale), ptr(xgrad),
+                                      float(epsilon) if epsilon is not None else 0.0, ptr(xadv), ptr(losses), _stream()))
+        return xgrad, xadv, losses
+
 
 class KernelProbe:
     """with KernelProbe(max_launches) as kp: ...launch steps...  -> kp.launches = [(kernel expression, microseconds)]

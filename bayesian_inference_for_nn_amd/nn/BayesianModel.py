@@ -23,6 +23,7 @@ class BayesianModel:
         self._distributions = []
         self._model = model
         self._plan = None
+        self._grad_plan = None      # adversarial_examples: a plan of its own, it carries the loss
 
     # ------------------------------------------------------------------ distributions
     def apply_distribution(self, distribution, start_layer: int, end_layer: int):
@@ -150,6 +151,49 @@ class BayesianModel:
         mean = mean_h.numpy()
         self._model.set_flat(Wd[-1].cpu().numpy())      # the reference leaves the last draw assigned
         return [Array(s) for s in samples], Array(mean)
+
+    def adversarial_examples(self, x, y, loss: str, epsilon: float, nb_samples: int):
+        """(x_adv, x_grad) as NumPy arrays: x_grad = sum over nb_samples weight draws of the gradient of the draw's mean
+        loss over all rows with respect to x, x_adv = x + epsilon * sign(x_grad) -- the FGSM step of
+        Robustness.adversarial_robustness (visualisations/Robustness.py:127-137), the sum over draws inside one device
+        GEMM (pyz_input_grad).  loss: "scce" (y = integer labels) or "mse" (y = targets)."""
+        import torch
+        from ..engine import MLPPlan, MLPSpec
+        if loss not in ("scce", "mse"):
+            raise ValueError(f"loss must be 'scce' or 'mse', not {loss!r}")
+        spec = MLPSpec(tuple(self._model.spec.dims), tuple(self._model.spec.acts), loss)
+        if (loss == "scce") != (spec.acts[-1] == "softmax"):
+            raise ValueError("'scce' needs a softmax last layer, 'mse' a last layer that is not softmax")
+        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+        shape = x.shape
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
+        n = len(x)
+        y = np.asarray(y.numpy() if hasattr(y, "numpy") else y)
+        if loss == "scce":
+            y = np.ascontiguousarray(y.reshape(-1).astype(np.int32))
+        else:
+            y = np.ascontiguousarray(y.astype(np.float32).reshape(n, -1))
+        if n < 1 or len(y) != n:
+            raise ValueError("x and y must hold the same, positive number of rows")
+        nb_samples = int(nb_samples)
+        Wd = self.sample_weights_device(nb_samples)
+        rows = min(n, int(self._predict_rows_cap))       # the workspace rule of predict
+        per = 2 * sum(int(d) for d in self._model.dims[1:])
+        chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
+        plan = self._grad_plan
+        if plan is None or plan.spec != spec or plan.max_batch < rows or plan.max_particles < chunk_s:
+            plan = self._grad_plan = MLPPlan(spec, max_batch=rows, max_particles=chunk_s)
+        xd, yd = torch.as_tensor(x).cuda(), torch.as_tensor(y).cuda()
+        grad = torch.empty_like(xd)
+        adv = torch.empty_like(xd)
+        for r0 in range(0, n, rows):
+            xc, yc = xd[r0:r0 + rows].contiguous(), yd[r0:r0 + rows].contiguous()
+            # a chunk's mean loss is over its own rows: chunk_rows / n of it is its share of the mean over all n
+            g, a, _ = plan.input_grad(Wd, xc, yc, scale=len(xc) / n, epsilon=float(epsilon))
+            grad[r0:r0 + rows] = g
+            adv[r0:r0 + rows] = a
+        plan.check_finite()
+        return adv.cpu().numpy().reshape(shape), grad.cpu().numpy().reshape(shape)
 
     # ------------------------------------------------------------------ persistence
     @classmethod

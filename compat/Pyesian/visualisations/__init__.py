@@ -3,6 +3,8 @@ for the driver scripts' `Metrics(model, dataset).summary()` and `Plotter(...)` c
 
 import numpy as np
 
+from bayesian_inference_for_nn_amd.visualisations import Robustness  # noqa: F401  (the library's own, not a stand-in)
+
 
 class Metrics:
     def __init__(self, model, dataset):

@@ -393,6 +393,16 @@ int pyz_svgd_kernel_matrix_groups(pyz_mlp *mlp, const double *d_groups, const fl
 int pyz_predict(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, int n,
                 float *d_samples, float *d_mean, void *stream);
 
+/* ---- R2: the input gradient of Robustness.adversarial_robustness (visualisations/Robustness.py:115-144):
+ * d_xgrad (n, dims[0]) = scale * sum_s d loss_s / d x over the n_samples draws d_weights (n_samples, D), loss_s =
+ * draw s's mean loss over the n contiguous rows of d_x (no row gather; d_y as for pyz_mlp_loss_grad), summed inside
+ * one GEMM over (draw, hidden unit) in a fixed order (the same bits on every call).  Optional: d_xadv (n, dims[0]) =
+ * d_x + epsilon * sign(d_xgrad) with sign(0) = 0 and NaN kept (the FGSM step), d_loss (n_samples) = each draw's mean
+ * loss.  Draws go through the plan in chunks of its max_particles; n <= max_batch.  A non-finite loss counts in the
+ * plan's counter (pyz_check_finite); nothing is masked. */
+int pyz_input_grad(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, const void *d_y, int n,
+                   float scale, float *d_xgrad, float epsilon, float *d_xadv, float *d_loss, void *stream);
+
 /* ---- noise: d_out[i] = mean + std * z_i, z from Philox stream (seed, stream, step).
  * (tf.random.normal at SGLD.py:67, HMC.py:171; tfp samplers at BBB.py:234-237,
  * SVGD.py:154, distributions/tf/TensorflowProbabilityDistribution.py:55-58.) */
