@@ -13,6 +13,7 @@
 #include "pyz_hmc_multi.h"
 #include "pyz_input_grad.h"
 #include "pyz_kernels.h"
+#include "pyz_predict_moments.h"
 #include "pyz_rng.h"
 
 namespace {
@@ -2698,6 +2699,35 @@ int pyz_predict(pyz_mlp *m, const float *d_weights, int n_samples, const float *
                softmax, n, d_samples ? d_samples + (long long)s0 * n * C : nullptr);
     PYZ_LAUNCH(k_predict_mean, dim3((unsigned)cdiv((long long)n * C, 256)), dim3(256), 0, st, m->act[m->L - 1],
                (long long)m->max_batch * C, (long long)n * C, S, d_mean, s0 > 0 ? 1 : 0, 1.0f / (float)n_samples);
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_predict_moments(pyz_mlp *m, const float *d_weights, int n_samples, const float *d_x, int n, float *d_mean,
+                        float *d_m2, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_samples <= 0 || n <= 0) return pyz_fail(PYZ_E_INVALID, "n_samples and n must be positive");
+  if (n > m->max_batch) return pyz_fail(PYZ_E_SHAPE, "n %d exceeds the plan's max_batch %d", n, m->max_batch);
+  if (!d_weights || !d_x || !d_mean || !d_m2) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  int rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st);
+  if (rc) return rc;
+  PredictMomentsArgs g{};
+  g.last = m->act[m->L - 1];
+  g.C = m->dims[m->L];
+  g.pstride = (long long)m->max_batch * g.C;
+  g.softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
+  g.n = n;
+  g.mean = d_mean;
+  g.m2 = d_m2;
+  g.inv_total = 1.0f / (float)n_samples;
+  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
+    g.S = std::min(m->max_p, n_samples - s0);
+    g.accumulate = s0 > 0 ? 1 : 0;
+    launch_forward(m, d_weights + (long long)s0 * m->D, m->D, g.S, d_x, nullptr, n, m->ctl, st);
+    if (!pyz_launch_predict_moments(g, st))
+      return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the moments kernel's LDS", g.C);
   }
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;

@@ -544,6 +544,23 @@ class MLPPlan:
         check(self.lib.pyz_predict(self.h, ptr(weights), S, ptr(x), n, ptr(samples), ptr(mean), _stream()))
         return samples, mean
 
+    def predict_moments(self, weights, x):
+        """(mean (n, out), m2 (n, out, out)) of the draws `weights` (S, D) on the rows of x: mean is predict's mean bit for
+        bit, m2[j] = sum over the draws of p p^T with p = predict's sample of row j.  One kernel per chunk of
+        max_particles draws (pyz_predict_moments); the (S, n, out) sample tensor is never formed."""
+        _f32(weights, name="weights")
+        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
+            raise ValueError(f"weights must be (draws >= 1, {self.D})")
+        _f32(x, name="x")
+        if x.dim() != 2 or x.shape[1] != self.spec.dims[0]:
+            raise ValueError(f"x must be (rows, {self.spec.dims[0]})")
+        n, C_out = int(x.shape[0]), self.spec.dims[-1]
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
+        m2 = torch.empty((n, C_out, C_out), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_predict_moments(self.h, ptr(weights), int(weights.shape[0]), ptr(x), n, ptr(mean), ptr(m2),
+                                           _stream()))
+        return mean, m2
+
     # ------------------------------------------------------------------ R2
     def input_grad(self, weights, x, y, scale=1.0, epsilon=None):
         """(xgrad, xadv or None, losses): xgrad (n, in) = scale * sum over the draws `weights` (S, D) of the gradient of

@@ -152,6 +152,51 @@ class BayesianModel:
         self._model.set_flat(Wd[-1].cpu().numpy())      # the reference leaves the last draw assigned
         return [Array(s) for s in samples], Array(mean)
 
+    def _read_out(self, x, nb_samples: int, moments: bool):
+        """predict's draws, row cap and workspace rule; per row chunk MLPPlan.predict_moments (moments) or the mean-only
+        MLPPlan.predict: device (mean (n, C), m2 (n, C, C) or None).  No sample tensor is formed."""
+        import torch
+        from ..engine import MLPPlan
+        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
+        nb_samples = int(nb_samples)
+        Wd = self.sample_weights_device(nb_samples)
+        n = len(x)
+        rows = min(n, int(self._predict_rows_cap))
+        per = 2 * sum(int(d) for d in self._model.dims[1:])
+        chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
+        if self._plan is None or self._plan.max_batch < rows or self._plan.max_particles < chunk_s:
+            self._plan = MLPPlan(self._model.spec, max_batch=rows, max_particles=chunk_s)
+        xd = torch.as_tensor(x).cuda()
+        C_out = int(self._model.dims[-1])
+        mean_full = m2_full = None
+        for r0 in range(0, n, rows):
+            xc = xd[r0:r0 + rows].contiguous()
+            mean_d, m2_d = self._plan.predict_moments(Wd, xc) if moments else (self._plan.predict(Wd, xc, want_samples=False)[1], None)
+            if rows >= n:
+                mean_full, m2_full = mean_d, m2_d
+            else:
+                if mean_full is None:
+                    mean_full = torch.empty((n, C_out), dtype=torch.float32, device=xd.device)
+                    m2_full = torch.empty((n, C_out, C_out), dtype=torch.float32, device=xd.device) if moments else None
+                mean_full[r0:r0 + rows] = mean_d
+                if moments:
+                    m2_full[r0:r0 + rows] = m2_d
+        self._model.set_flat(Wd[-1].cpu().numpy())      # the reference leaves the last draw assigned
+        return mean_full, m2_full
+
+    def predictive_moments(self, x, nb_samples: int):
+        """(mean (n, C), m2 (n, C, C), nb_samples) as NumPy float32 arrays: the Monte-Carlo mean of ``predict`` (bit for
+        bit, for the same draws) and, per row, the sum over the draws of p p^T -- all that
+        Metrics.classification_uncertainty needs of the draws.  Computed on the device by pyz_predict_moments: the
+        (nb_samples, n, C) sample tensor is neither written nor copied to the host."""
+        mean, m2 = self._read_out(x, nb_samples, True)
+        return mean.cpu().numpy(), m2.cpu().numpy(), int(nb_samples)
+
+    def predictive_mean(self, x, nb_samples: int):
+        """(n, C) NumPy float32: ``predict``'s mean alone (MLPPlan.predict without the sample tensor)."""
+        return self._read_out(x, nb_samples, False)[0].cpu().numpy()
+
     def adversarial_examples(self, x, y, loss: str, epsilon: float, nb_samples: int):
         """(x_adv, x_grad) as NumPy arrays: x_grad = sum over nb_samples weight draws of the gradient of the draw's mean
         loss over all rows with respect to x, x_adv = x + epsilon * sign(x_grad) -- the FGSM step of

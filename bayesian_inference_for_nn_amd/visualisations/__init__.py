@@ -1,3 +1,4 @@
+from .Metrics import Metrics
 from .Robustness import Robustness
 
-__all__ = ["Robustness"]
+__all__ = ["Metrics", "Robustness"]

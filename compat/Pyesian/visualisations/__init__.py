@@ -1,27 +1,9 @@
-"""Minimal stand-ins for the reference's evaluation helpers (out of the hot path's scope): enough
-for the driver scripts' `Metrics(model, dataset).summary()` and `Plotter(...)` calls to run."""
+"""`Metrics` and `Robustness` are the library's own; `Plotter` is a minimal stand-in (out of the hot path's scope): enough
+for the driver scripts' `Plotter(...)` calls to run."""
 
 import numpy as np
 
-from bayesian_inference_for_nn_amd.visualisations import Robustness  # noqa: F401  (the library's own, not a stand-in)
-
-
-class Metrics:
-    def __init__(self, model, dataset):
-        self._model = model[0] if isinstance(model, tuple) else model
-        self._dataset = dataset
-
-    def summary(self, nb_samples: int = 100):
-        x, y = self._dataset.test_data.as_numpy()
-        _, mean = self._model.predict(x, nb_samples)
-        mean = np.asarray(mean)
-        if self._dataset.likelihood_model == "Classification":
-            acc = float((mean.argmax(axis=1) == np.asarray(y).reshape(-1)).mean())
-            print(f"Accuracy: {100 * acc:.2f} %")
-            return {"accuracy": acc}
-        mse = float(((mean - np.asarray(y).reshape(mean.shape)) ** 2).mean())
-        print(f"MSE: {mse:.6f}")
-        return {"mse": mse}
+from bayesian_inference_for_nn_amd.visualisations import Metrics, Robustness  # noqa: F401  (the library's own, not stand-ins)
 
 
 class Plotter:

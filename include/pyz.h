@@ -393,6 +393,17 @@ int pyz_svgd_kernel_matrix_groups(pyz_mlp *mlp, const double *d_groups, const fl
 int pyz_predict(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, int n,
                 float *d_samples, float *d_mean, void *stream);
 
+/* The per-row moments of the same read-out, for callers that need the draws only through them
+ * (Metrics.classification_uncertainty, visualisations/Metrics.py): d_mean (n, out) as pyz_predict writes it, bit for bit,
+ * and d_m2 (n, out, out), d_m2[j][a][b] = sum_s p[s][j][a] * p[s][j][b] over the n_samples draws, p = pyz_predict's
+ * samples (softmax applied where the last activation is softmax, NaN -> 0) -- which are never written: one kernel per
+ * chunk of max_particles draws reads the last layer's outputs once and keeps the sums in registers.  Every element is a
+ * sequential float32 sum in draw order (the same bits on every call and for every max_particles; d_m2 is symmetric bit
+ * for bit).  Both outputs are required; rows >= n of neither are written; n <= max_batch.  out beyond ~13 000 (a row
+ * no longer fits a compute unit's LDS) is refused with PYZ_E_SHAPE. */
+int pyz_predict_moments(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, int n,
+                        float *d_mean, float *d_m2, void *stream);
+
 /* ---- R2: the input gradient of Robustness.adversarial_robustness (visualisations/Robustness.py:115-144):
  * d_xgrad (n, dims[0]) = scale * sum_s d loss_s / d x over the n_samples draws d_weights (n_samples, D), loss_s =
  * draw s's mean loss over the n contiguous rows of d_x (no row gather; d_y as for pyz_mlp_loss_grad), summed inside
