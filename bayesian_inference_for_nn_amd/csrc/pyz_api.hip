@@ -1440,6 +1440,7 @@ int pyz_bbb_step(pyz_mlp *m, float *d_mu, float *d_rho, float *d_w, const float 
   a.nblk_loss = loss_nblk(m, batch);
   a.ctl = m->ctl;
   a.cost = d_cost;
+  a.nonfinite = m->nonfinite;
   PYZ_LAUNCH(k_bbb_sample, dim3(nblk_kl), dim3(256), 0, st, a);
   WgradArgs u{};
   if (can_fuse(m)) {  // the mu / rho update runs in the epilogue of the weight-gradient kernel

@@ -554,6 +554,7 @@ struct BbbArgs {
   const StepCtl *ctl;
   float *cost;           // [0] = cost, [1] = data loss, [2] = log q - log p
   int chained;           // device-resident run: the Philox step is ctl->n
+  int *nonfinite;        // device counter of steps with a NaN / Inf cost (pyz_check_finite; may be nullptr)
 };
 
 __device__ __forceinline__ void pyz_bbb_eps(const BbbArgs &g, long long t, float *z) {
@@ -653,6 +654,7 @@ __global__ void k_bbb_update(BbbArgs g) {
       const float loss = (float)(sl / (double)g.ctl->batch);
       const float kl = (float)sk;
       g.cost[0] = loss + g.alpha * kl;
+      pyz_note_loss(g.nonfinite, g.cost[0]);
       g.cost[1] = loss;
       g.cost[2] = kl;
     }

@@ -193,25 +193,33 @@ def check_particles(P: int):
     return sorted({0, P // 2, P - 1})
 
 
-def close_blocks(grad, ref, spec: o_mlp.MLPSpec, rel: float = 1e-4, what: str = "grad"):
+def close_blocks(grad, ref, spec: o_mlp.MLPSpec, rel: float = 1e-4, what: str = "grad", state=None) -> float:
     """Each layer's W and b block against the reference on its own scale:
     max|g - r| <= rel * max(max|r_block|, 1e-3 * max|r|).  The floor only keeps a block of exact zeros (dead units)
-    from demanding bit equality."""
+    from demanding bit equality.  `state` (for a difference of two stored float32 vectors: the vector of their larger
+    magnitudes) adds 2^-23 * max|state_block| to a block's tolerance: the two float32 roundings of what was stored.
+    Returns the largest error over tolerance of any block."""
     grad = np.asarray(grad.detach().cpu().numpy() if hasattr(grad, "detach") else grad, dtype=np.float64).reshape(-1)
     ref = np.asarray(ref, dtype=np.float64).reshape(-1)
     assert grad.shape == ref.shape, (what, grad.shape, ref.shape)
     assert np.all(np.isfinite(grad)), f"{what}: non-finite gradient entries"
     floor = 1e-3 * np.abs(ref).max()
+    worst = 0.0
     for l, ((ko, bo), K, N) in enumerate(zip(spec.offsets(), spec.dims[:-1], spec.dims[1:])):
         for block, lo, shape in (("W", ko, (K, N)), ("b", bo, (N,))):
             g = grad[lo:lo + int(np.prod(shape))]
             r = ref[lo:lo + int(np.prod(shape))]
             scale = max(np.abs(r).max(), floor)
+            tol = rel * scale
+            if state is not None:
+                tol += 2.0 ** -23 * float(np.abs(np.asarray(state, dtype=np.float64).reshape(-1)[lo:lo + int(np.prod(shape))]).max())
             diff = np.abs(g - r)
             err = diff.max()
-            if not err <= rel * scale:
+            if not err <= tol:
                 i = int(diff.argmax())
                 at = tuple(map(int, np.unravel_index(i, shape)))
                 raise AssertionError(f"{what}: layer {l} block {block} {shape}: max err {err:.3e} at {at} "
-                                     f"(gpu {g[i]:.6e}, ref {r[i]:.6e}) vs block scale {scale:.3e} "
+                                     f"(gpu {g[i]:.6e}, ref {r[i]:.6e}) vs block scale {scale:.3e}, tolerance {tol:.3e} "
                                      f"(rel {err / max(scale, 1e-300):.3e} > {rel:g})")
+            worst = max(worst, err / tol if tol > 0 else 0.0)
+    return worst
