@@ -9,7 +9,7 @@ import os
 from . import _build
 
 ACT = {"linear": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "softmax": 4}
-LOSS = {"scce": 0, "mse": 1}
+LOSS = {"scce": 0, "mse": 1, "bce": 2}
 SWEEP = {"gauss_seidel": 0, "jacobi": 1}
 GAMMA_MEDIAN = -1.0       # PYZ_SVGD_GAMMA_MEDIAN
 

@@ -623,6 +623,8 @@ int check_loss_combo(const pyz_mlp *m) {
     return pyz_fail(PYZ_E_INVALID, "SparseCategoricalCrossentropy needs a softmax last layer");
   if (m->loss == PYZ_LOSS_MSE && last == PYZ_ACT_SOFTMAX)
     return pyz_fail(PYZ_E_INVALID, "MeanSquaredError on a softmax last layer is not supported");
+  if (m->loss == PYZ_LOSS_BCE && (m->dims[m->L] != 1 || last != PYZ_ACT_SIGMOID))
+    return pyz_fail(PYZ_E_INVALID, "BinaryCrossentropy needs a last layer of exactly one sigmoid unit");
   return PYZ_OK;
 }
 
@@ -697,7 +699,7 @@ int pyz_mlp_create(int n_layers, const int32_t *h_dims, const int32_t *h_acts, i
   if (n_layers < 1 || n_layers > PYZ_MAX_LAYERS) return pyz_fail(PYZ_E_INVALID, "n_layers %d outside [1, %d]", n_layers, PYZ_MAX_LAYERS);
   if (max_batch < 1 || max_particles < 1) return pyz_fail(PYZ_E_INVALID, "max_batch and max_particles must be >= 1");
   if (max_particles > 65535) return pyz_fail(PYZ_E_INVALID, "max_particles %d > 65535", max_particles);
-  if (loss != PYZ_LOSS_SCCE && loss != PYZ_LOSS_MSE) return pyz_fail(PYZ_E_INVALID, "unknown loss %d", loss);
+  if (loss != PYZ_LOSS_SCCE && loss != PYZ_LOSS_MSE && loss != PYZ_LOSS_BCE) return pyz_fail(PYZ_E_INVALID, "unknown loss %d", loss);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return pyz_fail(PYZ_E_NODEV, "no HIP device visible");
   pyz_mlp_full *m = new pyz_mlp_full();
@@ -724,6 +726,15 @@ int pyz_mlp_create(int n_layers, const int32_t *h_dims, const int32_t *h_acts, i
     off += (long long)(m->dims[l] + 1) * m->dims[l + 1];
   }
   m->D = off;
+  // the kernels read a BinaryCrossentropy target as ONE float per row: a plan of any other shape is refused here, for
+  // every entry point at once (the other two losses keep their per-call check: plans that only predict may carry any)
+  if (loss == PYZ_LOSS_BCE) {
+    const int rc = check_loss_combo(m);
+    if (rc != PYZ_OK) {
+      delete m;
+      return rc;
+    }
+  }
   {  // the kernels address operands with 32-bit byte offsets from per-layer bases (buffer descriptors)
     long long widest = 0;
     for (int l = 0; l <= n_layers; ++l) widest = std::max<long long>(widest, m->dims[l]);

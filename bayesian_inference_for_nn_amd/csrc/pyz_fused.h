@@ -170,6 +170,17 @@ __global__ void __launch_bounds__(512) k_head(HeadArgs g) {
           if (lvalid && ol) ol[c] = zv[q];
         }
       }
+    } else if (g.loss == PYZ_LOSS_BCE) {
+      // one sigmoid unit (N == 1: pyz_mlp_create), from its logit: the row's first lane has it
+      if (lsub == 0) {
+        const float yv = reinterpret_cast<const float *>(g.y)[yrow];
+        float o;
+        lm = pyz_bce_row(zv[0], yv, o);
+        const float dv = lvalid ? (o - yv) * (1.0f / (float)batch) : 0.0f;
+        d[0] = dv;
+        if (lvalid && dl) dl[0] = dv;
+        if (lvalid && ol) ol[0] = o;
+      }
     } else {
       const float *y = reinterpret_cast<const float *>(g.y) + yrow * N;
       const float sc = 2.0f / ((float)batch * (float)N);
@@ -425,6 +436,17 @@ __device__ __forceinline__ void pyz_head_row(const HeadArgs &g, const int batch,
         outv[c] = z[c];
       }
       lm = lse - zy;
+    } else if (NP == 4 && g.loss == PYZ_LOSS_BCE) {
+      // one sigmoid unit (N == 1: pyz_mlp_create; only the narrowest padding carries the arm), from its logit
+      const float yv = reinterpret_cast<const float *>(g.y)[yrow];
+      float o;
+      lm = pyz_bce_row(z[0], yv, o);
+      const float dv = (o - yv) * (1.0f / (float)batch);
+#pragma unroll
+      for (int c = 0; c < NP; ++c) {
+        d2[c] = c == 0 ? dv : 0.0f;
+        outv[c] = c == 0 ? o : 0.0f;
+      }
     } else {
       const float *y = reinterpret_cast<const float *>(g.y) + yrow * N;
       const float sc = 2.0f / ((float)batch * (float)N);

@@ -104,6 +104,22 @@ __device__ __forceinline__ float pyz_act_grad(float h, int act) {
   }
 }
 
+// BinaryCrossentropy row of ONE sigmoid unit from its logit z and target y in [0, 1] (DESIGN A7):
+// loss = max(z, 0) - z y + log1p(exp(-|z|)), p = sigmoid(z); delta = (p - y) / batch is the caller's.
+// exp only ever sees -|z|, so nothing overflows however far the unit saturates (log(1 + exp(z)) is inf past
+// z = 88.7, -log(1 - p) once p rounds to 1); a NaN logit still gives a NaN loss and p.
+__device__ __forceinline__ float pyz_bce_row(float z, float y, float &p) {
+  const float e = expf(-fabsf(z));  // in [0, 1]
+  const float r = 1.0f / (1.0f + e);
+  p = z >= 0.0f ? r : (z < 0.0f ? e * r : z);
+  // log1p(e) as log(u) e / (u - 1) with u = fl(1 + e): the quotient undoes the rounding of the sum, so the value is
+  // good to a few ulp down to e = 0 (u == 1: log1p(e) = e to float32).  The library's log1pf cost the small HMC kernels
+  // 2-4 registers each and four of them a wave of occupancy; this form costs none.
+  const float u = 1.0f + e;
+  const float l1p = u == 1.0f ? e : logf(u) * (e / (u - 1.0f));
+  return fmaxf(z, 0.0f) - z * y + l1p;
+}
+
 // Combine the S partial 32x32 tiles of a workgroup through LDS (fixed order)
 // and hand each element to `store(row_in_tile, col_in_tile, value)`.
 // C/D layout of v_mfma_f32_32x32x2_f32: col = lane & 31,

@@ -14,7 +14,7 @@
 //            recompute h_j, accumulate dW2[j][:], dW1[:][j], db1[j]; lane H+c accumulates db2[c];
 //            the 16 per-wave partials are combined in a fixed order
 // Supported: dims (I, H, C) with I <= 8, H <= 56, C <= 8 (H + C <= 64), hidden activation
-// relu/tanh/sigmoid/linear, softmax+SCCE or MSE output.  Anything else uses the generic path.
+// relu/tanh/sigmoid/linear, softmax+SCCE, MSE or (one sigmoid unit) BCE output.  Anything else uses the generic path.
 #pragma once
 
 #include <type_traits>
@@ -76,7 +76,7 @@ __device__ __forceinline__ double pyz_hf_block_sum(double v, double *sm) {
   return s;  // every thread gets the same total
 }
 
-// loss term of one row and its delta_out (SCCE on softmax logits / MSE), from the logits z[]
+// loss term of one row and its delta_out (SCCE on softmax logits / BCE on the one sigmoid logit / MSE), from the logits z[]
 template <int MC>
 __device__ __forceinline__ double pyz_hf_row_tail(const HmcFusedArgs &a, const float (&z)[MC], float *d, const float *yf,
                                                   const int r) {
@@ -100,6 +100,15 @@ __device__ __forceinline__ double pyz_hf_row_tail(const HmcFusedArgs &a, const f
 #pragma unroll
     for (int c = 0; c < MC; ++c) d[c] = c < C ? (expf(z[c] - lse) - (c == y ? 1.0f : 0.0f)) * inv : 0.0f;
     return (double)(lse - zy);
+  }
+  if (a.loss == PYZ_LOSS_BCE) {  // one sigmoid unit (C == 1: pyz_mlp_create), from its logit; yf holds one float per row
+    const float y = yf[r];
+    float o;
+    const float lm = pyz_bce_row(z[0], y, o);
+    const float dv = (o - y) * (1.0f / (float)N);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) d[c] = c == 0 ? dv : 0.0f;
+    return (double)lm;
   }
   const float sc = 2.0f / ((float)N * (float)C);
   float acc = 0.0f;

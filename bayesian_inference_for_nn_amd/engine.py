@@ -71,6 +71,9 @@ class MLPPlan:
     """Owns one `pyz_mlp` handle (device workspace for up to max_batch rows x max_particles)."""
 
     def __init__(self, spec: MLPSpec, max_batch: int, max_particles: int = 1, device=None):
+        if spec.loss == "bce" and (spec.dims[-1] != 1 or spec.acts[-1] != "sigmoid"):
+            raise ValueError("BinaryCrossentropy needs a last layer of exactly one sigmoid unit, not "
+                             f"{spec.dims[-1]} x '{spec.acts[-1]}'")
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("bayesian_inference_for_nn_amd needs an MI355X (no HIP device visible); there is no CPU path")

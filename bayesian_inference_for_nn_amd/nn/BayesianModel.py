@@ -201,14 +201,17 @@ class BayesianModel:
         """(x_adv, x_grad) as NumPy arrays: x_grad = sum over nb_samples weight draws of the gradient of the draw's mean
         loss over all rows with respect to x, x_adv = x + epsilon * sign(x_grad) -- the FGSM step of
         Robustness.adversarial_robustness (visualisations/Robustness.py:127-137), the sum over draws inside one device
-        GEMM (pyz_input_grad).  loss: "scce" (y = integer labels) or "mse" (y = targets)."""
+        GEMM (pyz_input_grad).  loss: "scce" (y = integer labels), "mse" (y = targets) or "bce" (y = 0/1
+        labels or targets in [0, 1], one per row)."""
         import torch
         from ..engine import MLPPlan, MLPSpec
-        if loss not in ("scce", "mse"):
-            raise ValueError(f"loss must be 'scce' or 'mse', not {loss!r}")
+        if loss not in ("scce", "mse", "bce"):
+            raise ValueError(f"loss must be 'scce', 'mse' or 'bce', not {loss!r}")
         spec = MLPSpec(tuple(self._model.spec.dims), tuple(self._model.spec.acts), loss)
-        if (loss == "scce") != (spec.acts[-1] == "softmax"):
-            raise ValueError("'scce' needs a softmax last layer, 'mse' a last layer that is not softmax")
+        if (loss == "scce") != (spec.acts[-1] == "softmax") or \
+                (loss == "bce" and (spec.dims[-1] != 1 or spec.acts[-1] != "sigmoid")):
+            raise ValueError("'scce' needs a softmax last layer, 'mse' a last layer that is not softmax, "
+                             "'bce' a last layer of one sigmoid unit")
         x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
         shape = x.shape
         x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))

@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from .. import losses
+from .Metrics import two_columns
 
 
 class Robustness:
@@ -35,6 +36,9 @@ class Robustness:
             stat = "Adversarial Robustness: " + str(robustness)
         else:
             y = np.asarray(self.y_true).reshape(-1)
+            # one output column is read as [1 - p, p], like Metrics: class 1 where the mean exceeds 0.5 (the reference's
+            # argmax over the single column is class 0 for every row)
+            predicted = two_columns(predicted.reshape(len(predicted), -1))[0]
             robustness = float((predicted.argmax(axis=1) == y).mean()) * 100
             stat = "Adversarial Robustness: " + str(robustness) + "%"
         if save_path:

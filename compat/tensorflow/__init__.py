@@ -152,7 +152,8 @@ keras = types.SimpleNamespace(
     models=types.SimpleNamespace(Sequential=Sequential, model_from_json=_model_from_json, Model=_DenseNet),
     layers=types.SimpleNamespace(Dense=Dense, Flatten=Flatten, InputLayer=InputLayer),
     losses=types.SimpleNamespace(SparseCategoricalCrossentropy=_losses.SparseCategoricalCrossentropy,
-                                 MeanSquaredError=_losses.MeanSquaredError),
+                                 MeanSquaredError=_losses.MeanSquaredError,
+                                 BinaryCrossentropy=_losses.BinaryCrossentropy),
     activations=types.SimpleNamespace(softmax=_softmax, relu=_named("relu"), tanh=_named("tanh"),
                                       sigmoid=_named("sigmoid"), linear=_named("linear")),
     utils=types.SimpleNamespace(to_categorical=_to_categorical),

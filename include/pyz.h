@@ -54,6 +54,7 @@ extern "C" {
 /* losses produced by Dataset.loss() (Pyesian/datasets/Dataset.py:152-159) */
 #define PYZ_LOSS_SCCE 0 /* SparseCategoricalCrossentropy on a softmax last layer; labels int32 (B) */
 #define PYZ_LOSS_MSE 1  /* MeanSquaredError; targets float32 (B, out) */
+#define PYZ_LOSS_BCE 2  /* BinaryCrossentropy on a last layer of ONE sigmoid unit, from its logit; targets float32 (B, 1) in [0, 1] */
 
 /* SVGD bandwidth: pass this as `gamma` for the median heuristic of SVGD.baseline__kernel (SVGD.py:165-181):
  * h = sqrt(0.5 median(sqdist) / log(M + 1)), K = exp(-sqdist / (2 h^2)), repulsion (-K X + X rowsum K) / h^2,
