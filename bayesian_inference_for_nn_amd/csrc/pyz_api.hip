@@ -2476,6 +2476,17 @@ static int svgd_gram_groups_impl(pyz_mlp *m, const float *d_all, int n_total, in
   return PYZ_OK;
 }
 
+// The Jacobi sweep reads every row of the snapshot while other workgroups of the same launch write d_particles: rows
+// written inside [d_all, d_all + M D) would be read half old, half new (neither sweep, not reproducible)
+static int svgd_check_snapshot(const pyz_mlp *m, const float *d_particles, int n_local, const float *d_all, int n_total, int sweep) {
+  if (sweep != PYZ_SWEEP_JACOBI || !m || !d_particles || !d_all) return PYZ_OK;
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(d_particles), a0 = reinterpret_cast<uintptr_t>(d_all);
+  const uintptr_t row = sizeof(float) * (uintptr_t)m->D;
+  if (p0 < a0 + (uintptr_t)n_total * row && a0 < p0 + (uintptr_t)n_local * row)
+    return pyz_fail(PYZ_E_INVALID, "the Jacobi sweep needs a snapshot separate from the rows it writes (d_particles overlaps d_all)");
+  return PYZ_OK;
+}
+
 static int svgd_check_gradients(const pyz_mlp *m, int n_local) {
   if (!m->grad || m->grad_owner != 1 || m->grad_rows != n_local)
     return pyz_fail(PYZ_E_INVALID, "no gradients of these %d particles in the plan: pyz_svgd_gradients must be the last "
@@ -2489,6 +2500,7 @@ static int svgd_combine_impl(pyz_mlp *m, float *d_particles, int n_local, const 
   if (rc) return rc;
   if (!d_particles || !d_all || !d_adam_m || !d_adam_v || !d_loss) return pyz_fail(PYZ_E_INVALID, "null device pointer");
   if (t < 1) return pyz_fail(PYZ_E_INVALID, "Adam step t must be >= 1");
+  if ((rc = svgd_check_snapshot(m, d_particles, n_local, d_all, n_total, PYZ_SWEEP_JACOBI))) return rc;
   if ((rc = svgd_check_gradients(m, n_local))) return rc;
   if (!m->km_valid || m->km_all != d_all || m->km_total != n_total || m->km_row0 != row0 || m->km_local != n_local || m->km_gamma != gamma)
     return pyz_fail(PYZ_E_INVALID, "pyz_svgd_combine without the kernel matrix of this snapshot (pyz_svgd_kernel_matrix with the "
@@ -2523,6 +2535,7 @@ static int svgd_sweep_impl(pyz_mlp *m, float *d_particles, int n_local, const fl
   if (sweep != PYZ_SWEEP_GAUSS_SEIDEL && sweep != PYZ_SWEEP_JACOBI) return pyz_fail(PYZ_E_INVALID, "unknown sweep %d", sweep);
   if (sweep == PYZ_SWEEP_GAUSS_SEIDEL && (d_all != d_particles || n_local != n_total))
     return pyz_fail(PYZ_E_INVALID, "the Gauss-Seidel sweep needs the whole particle matrix on this device");
+  if ((rc = svgd_check_snapshot(m, d_particles, n_local, d_all, n_total, sweep))) return rc;
   if ((rc = svgd_check_gradients(m, n_local))) return rc;
   const int tiles_on = pyz_env_int("PYZ_SVGD_TILES", 1);  // read per call: tests flip it
   const bool tile_ok = sweep == PYZ_SWEEP_JACOBI && svgd_tile_shape(n_local, n_total, row0, d_all, d_particles);
@@ -2685,6 +2698,7 @@ int pyz_svgd_step(pyz_mlp *m, float *d_particles, int n_local, const float *d_al
   // at -- are rows [row0, row0 + n_local) of the snapshot
   if (!d_all || !d_particles) return pyz_fail(PYZ_E_INVALID, "null device pointer");
   if (n_total < n_local || row0 < 0 || row0 + n_local > n_total) return pyz_fail(PYZ_E_INVALID, "rows [%d, %d) outside the %d particles", row0, row0 + n_local, n_total);
+  if (n_local > 0 && svgd_check_snapshot(m, d_particles, n_local, d_all, n_total, sweep)) return PYZ_E_INVALID;   // (before the gradient pass)
   const float *cur = (sweep == PYZ_SWEEP_JACOBI && d_all != d_particles && m) ? d_all + (long long)row0 * m->D : d_particles;
   const int rc = svgd_gradients_impl(m, cur, n_local, d_x, d_y, d_row_idx, batch, as_stream(stream));
   if (rc) return rc;

@@ -836,7 +836,7 @@ __global__ void __launch_bounds__(256) k_svgd_dist(SvgdArgs g) {
   const int j0 = blockIdx.y * 8;
   const long long base = (long long)blockIdx.x * PYZ_SVGD_BLOCK_ELEMS + (long long)w * PYZ_SVGD_PASS * 256;
   const float *xi_p = g.all + (long long)i * g.D;
-  const bool vec_ok = (g.D % 4 == 0);   // rows 16-B aligned
+  const bool vec_ok = (g.D % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.all) & 15) == 0);   // every row 16-B aligned
   float xi[PYZ_SVGD_PASS][4], xj[8][PYZ_SVGD_PASS][4];
 #pragma unroll
   for (int ps = 0; ps < PYZ_SVGD_PASS; ++ps) {
@@ -1027,7 +1027,7 @@ __global__ void __launch_bounds__(256) k_svgd_dist_tile(SvgdTileArgs g) {
   }
   const int blk = blockIdx.x + g.blk0;
   const long long base = (long long)blk * g.range;
-  const bool vec_ok = (g.D % 4 == 0);
+  const bool vec_ok = (g.D % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.all) & 15) == 0);   // every row 16-byte aligned
   double acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)

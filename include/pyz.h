@@ -326,8 +326,11 @@ int pyz_hmc_run_info(const pyz_mlp *mlp, int32_t *h_captures);
 
 /* ---- V2-V4: SVGD.step (SVGD.py:84-141).  d_particles (P_local, D) float32 are
  * this rank's rows [row0, row0+P_local) of the (M, D) particle matrix; d_all
- * (M, D) is the matrix the kernel row is evaluated against (== d_particles on
- * one GPU; the all-gathered snapshot under PYZ_SWEEP_JACOBI).  d_adam_m/v are
+ * (M, D) is the matrix the kernel row is evaluated against (== d_particles under
+ * PYZ_SWEEP_GAUSS_SEIDEL; under PYZ_SWEEP_JACOBI a SEPARATE snapshot -- the all-gathered
+ * matrix, or on one GPU a copy or the other of two alternating buffers: every row is
+ * read from it while d_particles is written, so a d_particles that overlaps
+ * [d_all, d_all + M D) is refused with PYZ_E_INVALID before anything is enqueued).  d_adam_m/v are
  * the Keras-legacy-Adam slots (P_local, D); t is the 1-based Adam step.  The
  * squared distances, the RBF kernel and the repulsion sum are evaluated in float64.  gamma > 0 is
  * the fixed bandwidth (reference: 1.0); PYZ_SVGD_GAMMA_MEDIAN selects the median heuristic.  d_loss[0] = sum_i loss_i / M over the
