@@ -15,6 +15,7 @@
 #include "pyz_kernels.h"
 #include "pyz_predict_moments.h"
 #include "pyz_rng.h"
+#include "pyz_sgld_chains.h"
 
 namespace {
 
@@ -1393,6 +1394,132 @@ int pyz_sgld_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, co
                  int64_t slot0, uint64_t seed, float *d_losses, int use_graph, void *stream) {
   return sgld_run_impl(m, d_theta, d_mean, d_sq_mean, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, n0, slot0, seed,
                        d_losses, use_graph, stream);
+}
+
+// ---- SGLD, P chains per launch (pyz_sgld_chains.h).  One step = the particle-batched gradient pass of pyz_svgd_gradients
+// (all chains on ONE batch, PYZ_UPD_NONE into the plan's (P, D) gradient buffer, per-particle losses in the plan's scalars)
+// and k_sgld_update_chains behind it.
+static int sgld_chains_check(const pyz_mlp *m, const void *theta, const void *mean, const void *sq, int n_chains,
+                             const void *x, const void *y, const void *losses, int64_t n) {
+  if (n_chains < 1) return pyz_fail(PYZ_E_INVALID, "n_chains %d: at least one chain", n_chains);
+  if (n < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
+  if (!theta || !mean || !sq || !x || !y || !losses) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_chains > m->max_p)
+    return pyz_fail(PYZ_E_SHAPE, "n_chains %d outside [1, %d] of the plan", n_chains, m->max_p);
+  return check_loss_combo(m);
+}
+
+static void launch_sgld_chains_step(pyz_mlp *m, float *theta, float *mean, float *sq, int P, const float *x, const void *y,
+                                    const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
+                                    uint64_t seed, const float *unit_noise, float *loss, hipStream_t st) {
+  const StepCtl *ctl = m->ctl + slot;
+  WgradArgs u{};
+  u.mode = PYZ_UPD_NONE;
+  u.grad = m->grad;
+  u.grad_pstride = m->D;
+  const bool fused = can_fuse(m);
+  if (fused) u.ploss = m->scal;      // per-particle losses in the weight-gradient launch (every particle's spare workgroup)
+  launch_loss_backward(m, theta, m->D, P, x, y, row_idx, grid_batch, ctl, true, u, st);
+  if (!fused) PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, ctl, m->scal, m->nonfinite);
+  SgldChainsArgs a{};
+  a.theta = theta;
+  a.mean = mean;
+  a.sq_mean = sq;
+  a.grad = m->grad;
+  a.D = m->D;
+  a.grad_pstride = m->D;
+  a.groups = (m->D + 3) / 4;
+  a.ctl = ctl;
+  a.next = chained ? m->ctl + (slot ^ 1) : nullptr;
+  a.tab_bs = m->tab_bs;
+  a.tab_lr = m->tab_lr;
+  a.row_stride = row_stride;
+  a.seed = seed;
+  a.unit_noise = unit_noise;
+  a.ploss = m->scal;
+  a.loss = loss;
+  a.loss_indexed = chained ? 1 : 0;
+  // the launch fills the chip once: 8 workgroups of 256 threads per CU over all chains (see pyz_sgld_chains.h)
+  const long long per_chain = std::max<long long>(1, 8LL * pyz_cu_count() / P);
+  const dim3 grid((unsigned)std::min<long long>(cdiv(a.groups, 256), per_chain), (unsigned)P);
+  PYZ_LAUNCH(k_sgld_update_chains, grid, dim3(256), 0, st, a);
+}
+
+int pyz_sgld_chains_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_chains, const float *d_x,
+                         const void *d_y, const int32_t *d_row_idx, int batch, float lr, int64_t n, uint64_t seed,
+                         const float *d_unit_noise, float *d_loss, void *stream) {
+  int rc = sgld_chains_check(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_loss, n);
+  if (rc) return rc;
+  if ((rc = check_call(m, n_chains, batch))) return rc;
+  if ((rc = need_grad(m, n_chains))) return rc;
+  hipStream_t st = as_stream(stream);
+  set_ctl_lazy(m, batch, lr, n);   // the first kernel of the pass carries the step scalars
+  launch_sgld_chains_step(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, batch, 0, false, 0, seed,
+                          d_unit_noise, d_loss, st);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// The run enqueues its steps one after the other (no graph: use_graph is accepted and pyz_last_run_info reports every step
+// as eager).  Each step is launched for ITS OWN batch size -- the host has the sizes -- so that its launches are those of
+// pyz_sgld_chains_step, whose weight-gradient launch picks its waves from the batch it is launched for: that is what makes
+// the run equal the step calls bit for bit on ragged batches.  The scalars the kernels read still come from the device
+// tables (StepCtl ping-pong, advanced by k_sgld_update_chains), so nothing waits for the host between two steps.
+int pyz_sgld_chains_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_chains, const float *d_x,
+                        const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
+                        int n_steps, int64_t n0, int64_t slot0, uint64_t seed, float *d_losses, int use_graph,
+                        void *stream) {
+  (void)use_graph;
+  int rc = sgld_chains_check(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_losses, n0);
+  if (rc) return rc;
+  if (!d_row_idx || !h_batch_sizes || !h_lr) return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "n_steps must be positive");
+  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "slot0 out of range");
+  for (int s = 0; s < n_steps; ++s)
+    if (h_batch_sizes[s] <= 0 || h_batch_sizes[s] > m->max_batch)
+      return pyz_fail(PYZ_E_SHAPE, "batch size %d of step %d outside [1, %d]", h_batch_sizes[s], s, m->max_batch);
+  if ((rc = need_grad(m, n_chains))) return rc;
+  pyz_mlp_full *f = full(m);
+  hipStream_t st = as_stream(stream);
+  // per-run tables (one padding entry: the last step prepares a slot nobody reads), as pyz_sgld_run sends them up
+  const size_t n_tab = (size_t)n_steps + 1;
+  if ((rc = ensure_run_tables(m, n_tab, 8, st))) return rc;
+  const long long row_stride = m->max_batch;
+  if (n_steps <= PYZ_INLINE_TAB) {
+    InlineTabs tabs{};
+    for (int s = 0; s < n_steps; ++s) {
+      tabs.bs[s] = h_batch_sizes[s];
+      tabs.lr[s] = h_lr[s];
+    }
+    tabs.bs[n_steps] = h_batch_sizes[n_steps - 1];
+    tabs.lr[n_steps] = h_lr[n_steps - 1];
+    tabs.n = n_steps + 1;
+    m->pend_on = false;
+    PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0);
+  } else {
+    const unsigned slot = (unsigned)(f->x.tab_count & 1);
+    if (f->x.tab_count >= 2) PYZ_HIP(hipEventSynchronize(f->x.tab_ev[slot]));
+    ++f->x.tab_count;
+    int32_t *hb = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(f->x.tab_host) + slot * f->x.tab_host_cap);
+    float *hl = reinterpret_cast<float *>(hb + n_tab);
+    std::memcpy(hb, h_batch_sizes, sizeof(int32_t) * n_steps);
+    std::memcpy(hl, h_lr, sizeof(float) * n_steps);
+    hb[n_steps] = h_batch_sizes[n_steps - 1];
+    hl[n_steps] = h_lr[n_steps - 1];
+    PYZ_HIP(hipMemcpyAsync(m->tab_bs, hb, sizeof(int32_t) * n_tab, hipMemcpyHostToDevice, st));
+    PYZ_HIP(hipMemcpyAsync(m->tab_lr, hl, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
+    PYZ_HIP(hipEventRecord(f->x.tab_ev[slot], st));
+    if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], n0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
+  }
+  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    launch_sgld_chains_step(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true,
+                            row_stride, seed, nullptr, d_losses, st);
+    ++m->run_eager_steps;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
 }
 
 // The SGD train loop (SGD.py:42-69 inside Optimizer.py:121-134) as one device-resident run: the launch sequence

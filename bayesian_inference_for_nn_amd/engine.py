@@ -238,6 +238,47 @@ class MLPPlan:
                                     n_steps, int(n0), int(slot0), int(seed), ptr(losses_out), 1 if use_graph else 0,
                                     _stream()))
 
+    def _check_chains(self, theta, mean, sq_mean):
+        P = int(theta.shape[0]) if theta.dim() == 2 else 0
+        if not 1 <= P <= self.max_particles:
+            raise ValueError(f"theta must be (n_chains, {self.D}) with 1 <= n_chains <= {self.max_particles}")
+        for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
+            _f32(t, (P, self.D), nm)
+        return P
+
+    def sgld_chains_step(self, theta, mean, sq_mean, x, y, lr, n, seed, loss_out, batch=None, row_idx=None, unit_noise=None):
+        """One SGLD step of the n_chains rows of theta / mean / sq_mean (n_chains, D) on ONE shared batch; chain c draws
+        the noise of seed + c (or row c of the (n_chains, D) unit_noise); loss_out: (n_chains,) float32."""
+        P = self._check_chains(theta, mean, sq_mean)
+        if unit_noise is not None:
+            _f32(unit_noise, (P, self.D), "unit_noise")
+        _f32(loss_out, (P,), "loss_out")
+        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+        self._check_xy(x, y, row_idx, batch)
+        check(self.lib.pyz_sgld_chains_step(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx),
+                                            batch, float(lr), int(n), int(seed), ptr(unit_noise), ptr(loss_out), _stream()))
+
+    def sgld_chains_run(self, theta, mean, sq_mean, x, y, row_idx, batch_sizes: Sequence[int], lrs: Sequence[float], n0, seed,
+                        losses_out, use_graph=True, slot0=0):
+        """n = len(batch_sizes) steps of sgld_chains_step without host work in between (see sgld_run for the tables);
+        losses_out: float32 (slots, n_chains), step s writes row slot0 + s."""
+        P = self._check_chains(theta, mean, sq_mean)
+        n_steps = len(batch_sizes)
+        assert len(lrs) == n_steps and n_steps > 0
+        self._check_xy(x, y, row_idx, 1)
+        if slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch:
+            raise ValueError("row_idx must hold (slot0 + n_steps) * max_batch entries")
+        _f32(losses_out, name="losses_out")
+        if losses_out.numel() < (slot0 + n_steps) * P:
+            raise ValueError("losses_out must hold (slot0 + n_steps) * n_chains entries")
+        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
+            raise ValueError("batch size outside the plan")
+        bs = (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes])
+        lr = (C.c_float * n_steps)(*[float(v) for v in lrs])
+        check(self.lib.pyz_sgld_chains_run(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx), bs,
+                                           lr, n_steps, int(n0), int(slot0), int(seed), ptr(losses_out),
+                                           1 if use_graph else 0, _stream()))
+
     def sgd_run(self, theta, x, y, row_idx, batch_sizes, lrs, losses_out, use_graph=True, slot0=0):
         """n = len(batch_sizes) SGD steps without host work in between (see sgld_run for the table layout)."""
         n_steps = len(batch_sizes)
@@ -274,7 +315,8 @@ class MLPPlan:
                                     1 if use_graph else 0, _stream()))
 
     def last_run_path(self):
-        """("graph" | "eager" | "mixed", steps) of the last sgld_run / sgd_run / swag_run / adam_run / bsam_run call on this plan."""
+        """("graph" | "eager" | "mixed", steps) of the last sgld_run / sgld_chains_run / sgd_run / swag_run / adam_run / bsam_run call on
+        this plan (sgld_chains_run: always "eager")."""
         g, e, n = C.c_int32(), C.c_int32(), C.c_int32()
         check(self.lib.pyz_last_run_info(self.h, C.byref(g), C.byref(e), C.byref(n)))
         kind = "graph" if e.value == 0 else ("eager" if g.value == 0 else "mixed")

@@ -133,17 +133,18 @@ class Optimizer(ABC):
             print()
 
     # ------------------------------------------------------------------ device-resident data
-    def _setup_backend(self, seed=None, max_particles=1, full_batch=False, chain_per_rank=True):
+    def _setup_backend(self, seed=None, max_particles=1, full_batch=False, chain_per_rank=True, chains_per_rank=1):
         """Builds the model, the kernel plan and the device copy of the training split.
         Several ranks (one process per GPU): every rank starts from the SAME base seed (the given one, else rank
-        0's entropy); independent chains (chain_per_rank) use base + rank, sharded SVGD the base itself -- its
+        0's entropy); independent chains (chain_per_rank) use base + rank -- base + rank * chains_per_rank where a rank
+        runs several chains that take consecutive seeds (SGLD's n_chains) --, sharded SVGD the base itself -- its
         ranks must draw one batch permutation and one particle initialisation."""
         import torch
         from .. import parallel
         from ..engine import MLPPlan, MLPSpec
         from ..nn.model import model_from_json
         self._rank, self._world = parallel.world_info()
-        self._seed = parallel.shared_seed(seed) + (self._rank if chain_per_rank else 0)
+        self._seed = parallel.shared_seed(seed) + (self._rank * int(chains_per_rank) if chain_per_rank else 0)
         self._rng = np.random.default_rng(self._seed)
         self._net = model_from_json(self._model_config)
         self._net.reset_glorot(self._rng)

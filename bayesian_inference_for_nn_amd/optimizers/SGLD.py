@@ -1,6 +1,13 @@
 """Stochastic Gradient Langevin Dynamics (mirrors Pyesian/optimizers/SGLD.py:14-166).
 Hyperparameters: batch_size, lr_upper, lr_lower, lr_gamma.  One fused device step: forward,
-loss, backward and the noise + parameter + running-moment update (three kernel launches)."""
+loss, backward and the noise + parameter + running-moment update (three kernel launches).
+
+Extension: kwarg n_chains = P > 1 runs P independent chains on one GPU in one particle-batched step (the reference has one
+chain).  Chain c of rank r has the seed base + r P + c for its Philox noise stream and for its Glorot start, so chain 0 of
+rank 0 starts where the one-chain optimizer with the same seed starts.  Each chain is a valid SGLD chain with its own noise
+and its own start, but the chains of a rank see the SAME minibatches (the rank's own): their gradient noise is shared, only
+the injected Langevin noise and the initial point are independent.  result() pools the chains' running moments,
+chain_results() gives one model per chain, r_hat() the Gelman-Rubin statistic between the chains."""
 
 import numpy as np
 
@@ -10,9 +17,34 @@ from ..nn import BayesianModel
 from .Optimizer import DeviceScalar, Optimizer
 
 
+def pool_chain_moments(mean, sq_mean):
+    """Running moments of P chains with equal step counts, pooled by parallel.merge_moment_chains' rule
+    sum_c n_c m_c / sum_c n_c = the average over chains, accumulated in float64.  mean, sq_mean: (P, D) arrays;
+    returns two float64 (D,) arrays."""
+    mean, sq_mean = np.asarray(mean, dtype=np.float64), np.asarray(sq_mean, dtype=np.float64)
+    return mean.sum(axis=0) / mean.shape[0], sq_mean.sum(axis=0) / sq_mean.shape[0]
+
+
+def gelman_rubin(mean, sq_mean, n: int):
+    """Gelman-Rubin R-hat per parameter from the running moments of P chains of n draws each ((P, D) arrays), in float64:
+    W = mean_c[(sq_c - mean_c^2) n / (n - 1)], B / n = var_c(mean_c, ddof=1), R-hat = sqrt(((n - 1) / n W + B / n) / W).
+    A parameter no chain moved (W = 0) gives NaN."""
+    mean, sq_mean = np.asarray(mean, dtype=np.float64), np.asarray(sq_mean, dtype=np.float64)
+    if mean.ndim != 2 or mean.shape[0] < 2:
+        raise ValueError("r_hat needs at least two chains")
+    if n < 2:
+        raise ValueError("r_hat needs at least two steps per chain")
+    n = float(n)
+    W = ((sq_mean - mean ** 2) * (n / (n - 1.0))).mean(axis=0)
+    B_over_n = mean.var(axis=0, ddof=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt(((n - 1.0) / n * W + B_over_n) / W)
+
+
 class SGLD(Optimizer):
     def __init__(self):
         super().__init__()
+        self._n_chains = 1
         self._n = None
         self._running_loss = None
         self._lr_upper = None
@@ -35,6 +67,11 @@ class SGLD(Optimizer):
         self._lr_upper = self._hyperparameters.lr_upper
         self._lr_lower = self._hyperparameters.lr_lower
         self._lr_gamma = self._hyperparameters.lr_gamma
+        self._n_chains = int(kwargs.get("n_chains", 1))
+        if self._n_chains < 1:
+            raise ValueError("n_chains must be at least 1")
+        if self._n_chains > 1:
+            return self._compile_chains(**kwargs)
         self._setup_backend(seed=kwargs.get("seed"))
         self._merge_ranks = bool(kwargs.get("merge_ranks", True))
         self._base_model = self._net
@@ -48,7 +85,46 @@ class SGLD(Optimizer):
         self._n = 0
         self._running_loss = 0
 
+    def _compile_chains(self, **kwargs):
+        """n_chains = P > 1: a plan for P particles and a (P, D) state; chain c starts from the Glorot draw of its own seed."""
+        import torch
+        from ..nn.model import model_from_json
+        P = self._n_chains
+        self._setup_backend(seed=kwargs.get("seed"), max_particles=P, chains_per_rank=P)   # self._seed = base + rank * P
+        self._merge_ranks = bool(kwargs.get("merge_ranks", True))
+        self._base_model = self._net
+        self._dataset_setup()
+        starts = [self._net.weights_flat.copy()]               # chain 0: reset_glorot(default_rng(self._seed)), done by the backend
+        for c in range(1, P):
+            scratch = model_from_json(self._model_config)
+            scratch.reset_glorot(np.random.default_rng(self._seed + c))
+            starts.append(scratch.weights_flat.copy())
+        self._theta = torch.as_tensor(np.stack(starts).astype(np.float32)).cuda()
+        self._mean_dev = torch.zeros((P, self._D), device="cuda")
+        self._sq_mean_dev = torch.zeros((P, self._D), device="cuda")
+        self._loss_dev = torch.zeros(P, device="cuda")
+        self._running_dev = torch.zeros(1, device="cuda")
+        self._weight_layers_indices = self._layer_indices()
+        self._n = 0
+        self._running_loss = 0
+
+    def _step_chains(self, save_document_path=None):
+        idx, b, _ = self._next_batch()
+        lr = float(self._lr(self._n))
+        self._plan.sgld_chains_step(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, lr, self._n,
+                                    self._seed, self._loss_dev, batch=b, row_idx=idx)
+        self._running_dev += self._loss_dev.mean()             # the mean over chains of the batch loss
+        if save_document_path != None:
+            with open(save_document_path, "a") as losses_file:
+                losses_file.write(str(float(self._loss_dev.mean().item())))
+        self._n += 1
+        return DeviceScalar(self._running_dev.clone(), 0, 1.0 / self._n)
+
     def step(self, save_document_path=None):
+        """One step; returns the running mean over steps of the batch loss (with n_chains > 1: of its mean over chains)
+        as a DeviceScalar -- nothing synchronises until somebody reads it."""
+        if self._n_chains > 1:
+            return self._step_chains(save_document_path)
         idx, b, _ = self._next_batch()
         lr = float(self._lr(self._n))
         self._plan.sgld_step(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, lr, self._n,
@@ -71,6 +147,15 @@ class SGLD(Optimizer):
         """verbose=False: all steps in one device-resident run (hipGraph replay, no host sync)."""
         import torch
         lrs = np.asarray(self._lr(self._n + np.arange(nb_iterations, dtype=np.float64))).astype(np.float32).tolist()
+        if self._n_chains > 1:
+            def launch_chains(idx, loss_buf, sizes, s0):
+                self._plan.sgld_chains_run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
+                                           lrs[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf, use_graph=True, slot0=s0)
+            losses = self._run_resident_chunks(nb_iterations, launch_chains)          # (nb_iterations, P)
+            self._running_dev += losses.mean(dim=1).sum()
+            self._n += nb_iterations
+            self.last_losses = losses.clone()
+            return True
 
         def launch(idx, loss_buf, sizes, s0):
             self._plan.sgld_run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
@@ -81,10 +166,64 @@ class SGLD(Optimizer):
         self.last_losses = losses.clone()          # the buffer itself is reused by the next run
         return True
 
+    def _reserve_resident(self, n_steps: int):
+        """With n_chains = P > 1 the loss buffer of the resident runs is (cap, P): a row per step."""
+        import torch
+        if self._n_chains == 1:
+            return super()._reserve_resident(n_steps)
+        if n_steps > getattr(self, "_res_cap", 0):
+            cap = max(256, 1 << (n_steps - 1).bit_length())
+            self._res_idx = torch.zeros((cap, self._plan.max_batch), dtype=torch.int32, device="cuda")
+            self._res_losses = torch.zeros((cap, self._n_chains), device="cuda")
+            self._res_cap = cap
+
     def update_parameters_step(self):
         return super().update_parameters_step()
 
+    def _model_from(self, mean, sq_mean, theta) -> BayesianModel:
+        """result()'s model from host float32 moments and weights: per layer Normal(loc = mean, scale = sq_mean - mean^2)."""
+        model = BayesianModel(self._model_config)
+        for sl, layer_idx in zip(self._spec.layer_slices(), self._weight_layers_indices):
+            dist = TensorflowProbabilityDistribution(tfd.Normal(mean[sl].copy(), (sq_mean[sl] - mean[sl] ** 2).copy()))
+            model.apply_distribution(dist, layer_idx, layer_idx)
+        model._model.set_flat(theta)
+        return model
+
+    def chain_results(self):
+        """One BayesianModel per chain of this rank, each built as result() builds its one from that chain's moments and
+        weights (no pooling, no merge across ranks)."""
+        mean, sq, theta = self._mean_dev.cpu().numpy(), self._sq_mean_dev.cpu().numpy(), self._theta.cpu().numpy()
+        if self._n_chains == 1:
+            mean, sq, theta = mean[None, :], sq[None, :], theta[None, :]
+        return [self._model_from(mean[c], sq[c], theta[c]) for c in range(self._n_chains)]
+
+    def r_hat(self):
+        """Gelman-Rubin R-hat of every parameter between this rank's chains, float64 (D,), from the running moments (see
+        gelman_rubin).  The moments run from step 0: there is no burn-in, so the chains' different starts count as
+        between-chain variance and R-hat comes down only as the run outgrows them.  ValueError for fewer than two chains
+        or fewer than two steps."""
+        if self._n_chains < 2:
+            raise ValueError("r_hat needs at least two chains (compile with n_chains >= 2)")
+        return gelman_rubin(self._mean_dev.cpu().numpy(), self._sq_mean_dev.cpu().numpy(), int(self._n))
+
+    def _result_chains(self) -> BayesianModel:
+        import torch
+        P = self._n_chains
+        mean64, sq64 = pool_chain_moments(self._mean_dev.cpu().numpy(), self._sq_mean_dev.cpu().numpy())
+        mean, sq_mean = mean64.astype(np.float32), sq64.astype(np.float32)
+        if self._world > 1 and self._merge_ranks:
+            # every rank pools its P chains first; the ranks' pools then merge with P n draws each
+            from .. import parallel
+            mean_dev, sq_dev, self.pooled_steps = parallel.merge_moment_chains(
+                torch.as_tensor(mean).cuda(), torch.as_tensor(sq_mean).cuda(), P * self._n)
+            mean, sq_mean = mean_dev.cpu().numpy(), sq_dev.cpu().numpy()
+        return self._model_from(mean, sq_mean, self._theta[0].cpu().numpy())     # the net's weights: chain 0's
+
     def result(self) -> BayesianModel:
+        """The posterior model.  With n_chains > 1 the chains' moments are pooled first (pool_chain_moments), the net's
+        weights are chain 0's."""
+        if self._n_chains > 1:
+            return self._result_chains()
         model = BayesianModel(self._model_config)
         mean_dev, sq_dev = self._mean_dev, self._sq_mean_dev
         if self._world > 1 and self._merge_ranks:

@@ -169,6 +169,29 @@ int pyz_sgld_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, 
                  const float *h_lr, int n_steps, int64_t n0, int64_t slot0, uint64_t seed,
                  float *d_losses, int use_graph, void *stream);
 
+/* SGLD, n_chains independent chains in one particle-batched step (an extension: the reference has one chain).
+ * d_theta / d_mean / d_sq_mean are float32 (n_chains, D) row-major, d_unit_noise too when given, d_loss float[n_chains].
+ * All chains take their gradients on the SAME batch (one particle-batched pass, as pyz_svgd_gradients); chain c then
+ * applies pyz_sgld_step's update to row c with z from the Philox stream (seed + c, step n), keyed by the element's index
+ * inside the chain: row c draws exactly what a single-chain pyz_sgld_step with seed + c draws.  d_loss[c] = chain c's
+ * batch loss.  n_chains must not exceed the plan's max_particles (PYZ_E_SHAPE).  Argument errors (a NULL pointer,
+ * n_chains < 1, n < 0, a batch or chain count outside the plan) return before anything touches the GPU. */
+int pyz_sgld_chains_step(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, int n_chains,
+                         const float *d_x, const void *d_y, const int32_t *d_row_idx, int batch, float lr,
+                         int64_t n, uint64_t seed, const float *d_unit_noise, float *d_loss /* [n_chains] */,
+                         void *stream);
+
+/* The train loop over pyz_sgld_chains_step without per-step host work: the arguments of pyz_sgld_run; step s uses slot
+ * slot0 + s of d_row_idx, h_batch_sizes[s], h_lr[s] and count n0 + s, and writes its n_chains losses to
+ * d_losses[(slot0 + s) * n_chains ..].  The per-step scalars live in device memory and are advanced by the last kernel
+ * of each step; nothing synchronises inside the call.  The steps are enqueued one after the other, each launched for its
+ * own batch size (no hipGraph, whatever use_graph says: pyz_last_run_info reports them as eager steps).  Results equal
+ * n_steps calls of pyz_sgld_chains_step bit for bit, on ragged batches and across epoch changes. */
+int pyz_sgld_chains_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, int n_chains,
+                        const float *d_x, const void *d_y, const int32_t *d_row_idx,
+                        const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0, int64_t slot0,
+                        uint64_t seed, float *d_losses /* (slots, n_chains) */, int use_graph, void *stream);
+
 /* Device-resident multi-step SGD (SGD.py:42-69 under the train loop of Optimizer.py:121-134): the
  * arguments of pyz_sgld_run without the moment vectors, count and seed; step s applies
  * theta <- theta - h_lr[s] * grad on its batch and writes the batch loss to d_losses[slot0+s].
