@@ -43,29 +43,23 @@ struct Extra {  // lazily sized buffers kept beside the plan
   size_t fwd_part_cap = 0;
   void *gs_res_buf = nullptr;  // k_svgd_gs_resident: epoch, fail flag, granules of the partials and of the kernel row
   size_t gs_res_cap = 0;
-  hipGraph_t hm_graph = nullptr;  // the launch sequence of one sliced HMC proposal
-  hipGraphExec_t hm_exec = nullptr;
-  unsigned long long hm_key = 0;
+  PyzGraphCache<1> hm_graphs;  // the launch sequence of one sliced HMC proposal
   double *part2 = nullptr;
   // per-run tables go up through two pinned buffers used in turn (an event each: rewritten only once its copy has left)
   void *tab_host = nullptr;
   size_t tab_host_cap = 0;  // bytes per buffer
   hipEvent_t tab_ev[2] = {};
   unsigned long long tab_count = 0;
-  // pyz_adam_run: the bias-correction pairs beside tab_bs / tab_lr, and what each cached graph was captured for (a graph
-  // of these runs bakes in the launch geometry of every step: the batch sizes of its chunk)
+  // pyz_adam_run: the bias-correction pairs beside tab_bs / tab_lr
   float2 *tab_bc = nullptr;
   int tab_bc_cap = 0;
-  // ... and these runs' own graph cache.  A graph holds steps of one batch size and starts on one StepCtl slot, and a quiet
+  // ... and these runs' own graph cache (a graph of these runs bakes in the launch geometry of every step: the batch size
+  // of its chunk, its signature).  A graph holds steps of one batch size and starts on one StepCtl slot, and a quiet
   // train() cuts its stretches of equal batches wherever its resident chunks end: stretch lengths 1 .. batches per epoch in
   // two parities, plus the ragged batch.  AR_GRAPHS slots keep all of them for epochs of up to ~14 batches; longer epochs
-  // mostly see full chunks.  ar_captures: graphs the last call had to capture (pyz_adam_run_info).
+  // mostly see full chunks.  Its captures: graphs the last call had to capture (pyz_adam_run_info).
   static constexpr int AR_GRAPHS = 32;
-  hipGraph_t ar_graph[AR_GRAPHS] = {};
-  hipGraphExec_t ar_exec[AR_GRAPHS] = {};
-  int ar_len[AR_GRAPHS] = {};
-  unsigned long long ar_sig[AR_GRAPHS] = {}, ar_use[AR_GRAPHS] = {}, ar_clock = 0, ar_key = 0;
-  int ar_captures = 0;
+  PyzGraphCache<AR_GRAPHS> adam_graphs;
   // per-proposal HMC scalars (uniforms + HmcCall) go up through a ring of pinned slots: a copy from pageable
   // memory would make every pyz_hmc_step wait for the stream, i.e. serialise the host with the device
   static constexpr int UP_SLOTS = 64;
@@ -84,11 +78,8 @@ struct Extra {  // lazily sized buffers kept beside the plan
   size_t hr_host_cap = 0;        // bytes per buffer
   hipEvent_t hr_ev[2] = {};
   unsigned long long hr_count = 0;
-  hipGraph_t hr_graph[PYZ_GRAPH_CHUNKS] = {};   // slot 0 = a chunk of proposals, the others = remainders by exact length (LRU)
-  hipGraphExec_t hr_exec[PYZ_GRAPH_CHUNKS] = {};
-  int hr_len[PYZ_GRAPH_CHUNKS] = {};
-  unsigned long long hr_use[PYZ_GRAPH_CHUNKS] = {}, hr_clock = 0, hr_key = 0;
-  int hr_captures = 0;           // graphs the last pyz_hmc_run captured
+  // slot 0 = a chunk of proposals, the others = remainders by exact length (LRU); its captures: those of the last pyz_hmc_run
+  PyzGraphCache<PYZ_GRAPH_CHUNKS> hmc_run_graphs;
 };
 
 }  // namespace
@@ -101,36 +92,6 @@ struct pyz_mlp_full : pyz_mlp {
 namespace {
 
 inline pyz_mlp_full *full(pyz_mlp *m) { return static_cast<pyz_mlp_full *>(m); }
-
-void drop_hmc_run_graphs(Extra &x) {
-  for (int c = 0; c < PYZ_GRAPH_CHUNKS; ++c) {
-    if (x.hr_exec[c]) (void)hipGraphExecDestroy(x.hr_exec[c]);
-    if (x.hr_graph[c]) (void)hipGraphDestroy(x.hr_graph[c]);
-    x.hr_exec[c] = nullptr;
-    x.hr_graph[c] = nullptr;
-    x.hr_len[c] = 0;
-  }
-}
-
-void drop_adam_run_graphs(Extra &x) {
-  for (int c = 0; c < Extra::AR_GRAPHS; ++c) {
-    if (x.ar_exec[c]) (void)hipGraphExecDestroy(x.ar_exec[c]);
-    if (x.ar_graph[c]) (void)hipGraphDestroy(x.ar_graph[c]);
-    x.ar_exec[c] = nullptr;
-    x.ar_graph[c] = nullptr;
-    x.ar_len[c] = 0;
-  }
-}
-
-void drop_graphs(pyz_mlp *m) {
-  for (int c = 0; c < PYZ_GRAPH_CHUNKS; ++c) {
-    if (m->graph_exec[c]) (void)hipGraphExecDestroy(m->graph_exec[c]);
-    if (m->graph[c]) (void)hipGraphDestroy(m->graph[c]);
-    m->graph_exec[c] = nullptr;
-    m->graph[c] = nullptr;
-    m->graph_len[c] = 0;
-  }
-}
 
 int need_grad(pyz_mlp *m, int P) {
   m->grad_owner = 2;   // (pyz_svgd_gradients sets 1 after this call)
@@ -803,11 +764,10 @@ int pyz_mlp_create(int n_layers, const int32_t *h_dims, const int32_t *h_acts, i
 int pyz_mlp_destroy(pyz_mlp *mm) {
   if (!mm) return PYZ_OK;
   pyz_mlp_full *m = full(mm);
-  drop_graphs(m);
-  if (m->x.hm_exec) (void)hipGraphExecDestroy(m->x.hm_exec);
-  if (m->x.hm_graph) (void)hipGraphDestroy(m->x.hm_graph);
-  drop_hmc_run_graphs(m->x);
-  drop_adam_run_graphs(m->x);
+  m->graphs.drop();
+  m->x.hm_graphs.drop();
+  m->x.hmc_run_graphs.drop();
+  m->x.adam_graphs.drop();
   for (int l = 0; l < PYZ_MAX_LAYERS; ++l) {
     if (m->act[l]) (void)hipFree(m->act[l]);
     if (m->delta[l]) (void)hipFree(m->delta[l]);
@@ -1066,7 +1026,7 @@ static int ensure_run_tables(pyz_mlp *m, size_t n_tab, size_t host_entry_bytes, 
     PYZ_HIP(hipMalloc((void **)&m->tab_bs, 8 * cap));
     m->tab_lr = reinterpret_cast<float *>(m->tab_bs + cap);
     m->tab_cap = (int)cap;
-    drop_graphs(m);
+    m->graphs.drop();
   }
   // the tables go up through two pinned buffers used in turn: a buffer is rewritten once the copy of the run
   // before the previous one has left it (no stream-wide synchronisation per call)
@@ -1083,6 +1043,93 @@ static int ensure_run_tables(pyz_mlp *m, size_t n_tab, size_t host_entry_bytes, 
     f->x.tab_host_cap = cap;
     f->x.tab_count = 0;
   }
+  return PYZ_OK;
+}
+
+// What every run entry checks of its step count, its first slot and its batch sizes (h_epochs: the epoch counts of an ADAM /
+// VADAM run, checked step by step beside them).  Returns the largest batch of the call, or the error.
+// h_batch_sizes == nullptr: the first two checks alone, for an entry whose own checks stand between them and the third.
+static int check_run(const pyz_mlp *m, int n_steps, int64_t slot0, const int32_t *h_batch_sizes, const int64_t *h_epochs = nullptr) {
+  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "n_steps must be positive");
+  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "slot0 out of range");
+  int bmax = 0;
+  for (int s = 0; h_batch_sizes && s < n_steps; ++s) {
+    if (h_batch_sizes[s] <= 0 || h_batch_sizes[s] > m->max_batch)
+      return pyz_fail(PYZ_E_SHAPE, "batch size %d of step %d outside [1, %d]", h_batch_sizes[s], s, m->max_batch);
+    if (h_epochs && h_epochs[s] < 1) return pyz_fail(PYZ_E_INVALID, "epoch %lld of step %d < 1", (long long)h_epochs[s], s);
+    bmax = std::max(bmax, h_batch_sizes[s]);
+  }
+  return bmax;
+}
+
+// 1 - beta^epoch of every step of an ADAM / VADAM run, exactly as adam_scalars evaluates it for the eager step: the third table
+struct RunBc {
+  double beta_1, beta_2;
+  const int64_t *h_epochs;
+  float2 of(int s) const {
+    const AdamScal a = adam_scalars(0.0f, beta_1, beta_2, h_epochs[s], 0.0f, 0.0f);
+    return make_float2(a.bc1, a.bc2);
+  }
+};
+
+// Sends up the per-run tables (one padding entry: the last step prepares a slot nobody reads; with bc, the bias-correction
+// pairs beside batch sizes and learning rates) and sets the scalars of the first step.  ahead_batch > 0: the run assembles
+// its batches one step ahead, and the first one goes out here, placed for the forward tiles of a batch of ahead_batch rows.
+static int upload_run_tables(pyz_mlp *m, const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0, int64_t slot0,
+                             const RunBc *bc, const float *d_x, const int32_t *d_row_idx, int ahead_batch, hipStream_t st) {
+  Extra &x = full(m)->x;
+  int rc;
+  const size_t n_tab = (size_t)n_steps + 1;
+  if ((rc = ensure_run_tables(m, n_tab, bc ? 16 : 8, st))) return rc;
+  if (bc && x.tab_bc_cap < m->tab_cap) {   // (as large as the other tables: its address is baked into the graphs too)
+    if (x.tab_bc) PYZ_HIP(hipFree(x.tab_bc));
+    x.tab_bc = nullptr;
+    x.tab_bc_cap = 0;
+    PYZ_HIP(hipMalloc((void **)&x.tab_bc, sizeof(float2) * (size_t)m->tab_cap));
+    x.tab_bc_cap = m->tab_cap;
+  }
+  const long long row_stride = m->max_batch;
+  m->pend_on = false;
+  if (n_steps <= PYZ_INLINE_TAB) {
+    // short run: the tables ride in the arguments of the launch that sets the first step's scalars
+    InlineTabs tabs{};
+    InlineBc ibc{};
+    for (int s = 0; s < n_steps; ++s) {
+      tabs.bs[s] = h_batch_sizes[s];
+      tabs.lr[s] = h_lr[s];
+    }
+    tabs.bs[n_steps] = h_batch_sizes[n_steps - 1];
+    tabs.lr[n_steps] = h_lr[n_steps - 1];
+    tabs.n = n_steps + 1;
+    for (int s = 0; bc && s <= n_steps; ++s) ibc.bc[s] = bc->of(std::min(s, n_steps - 1));
+    if (ahead_batch) {   // ... together with the first batch of the run
+      const PrepArgs pa = prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0);
+      if (bc) PYZ_LAUNCH(k_run_start_bc, dim3(256), dim3(256), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, x.tab_bc, (long long)n0, slot0 * row_stride, (int)slot0, pa);
+      else PYZ_LAUNCH(k_run_start, dim3(256), dim3(256), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0, pa);
+    } else {
+      if (bc) PYZ_LAUNCH(k_set_ctl_tabs_bc, dim3(1), dim3(64), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, x.tab_bc, (long long)n0, slot0 * row_stride, (int)slot0);
+      else PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0);
+    }
+    return PYZ_OK;
+  }
+  const unsigned slot = (unsigned)(x.tab_count & 1);
+  if (x.tab_count >= 2) PYZ_HIP(hipEventSynchronize(x.tab_ev[slot]));
+  ++x.tab_count;
+  int32_t *hb = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(x.tab_host) + slot * x.tab_host_cap);
+  float *hl = reinterpret_cast<float *>(hb + n_tab);
+  float2 *hc = reinterpret_cast<float2 *>(hl + n_tab);   // (8 n_tab bytes in: aligned)
+  std::memcpy(hb, h_batch_sizes, sizeof(int32_t) * n_steps);
+  std::memcpy(hl, h_lr, sizeof(float) * n_steps);
+  hb[n_steps] = h_batch_sizes[n_steps - 1];
+  hl[n_steps] = h_lr[n_steps - 1];
+  for (int s = 0; bc && s <= n_steps; ++s) hc[s] = bc->of(std::min(s, n_steps - 1));
+  PYZ_HIP(hipMemcpyAsync(m->tab_bs, hb, sizeof(int32_t) * n_tab, hipMemcpyHostToDevice, st));
+  PYZ_HIP(hipMemcpyAsync(m->tab_lr, hl, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
+  if (bc) PYZ_HIP(hipMemcpyAsync(x.tab_bc, hc, sizeof(float2) * n_tab, hipMemcpyHostToDevice, st));
+  PYZ_HIP(hipEventRecord(x.tab_ev[slot], st));
+  if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], n0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
+  if (ahead_batch)   // the first batch of the run (every later one is assembled by the step before it)
+    PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0), m->ctl);
   return PYZ_OK;
 }
 
@@ -1231,18 +1278,12 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
   if (mode == PYZ_UPD_SGD) d_mean = d_sq_mean = d_theta;  // not touched in this mode
   int rc = check_loss_combo(m);
   if (rc) return rc;
-  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "n_steps must be positive");
-  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "slot0 out of range");
+  if ((rc = check_run(m, n_steps, slot0, nullptr)) < 0) return rc;
   if (!d_theta || !d_mean || !d_sq_mean || !d_x || !d_y || !d_row_idx || !h_batch_sizes || !h_lr || !d_losses)
     return pyz_fail(PYZ_E_INVALID, "null pointer");
-  int bmax = 0;
-  for (int s = 0; s < n_steps; ++s) {
-    if (h_batch_sizes[s] <= 0 || h_batch_sizes[s] > m->max_batch)
-      return pyz_fail(PYZ_E_SHAPE, "batch size %d of step %d outside [1, %d]", h_batch_sizes[s], s, m->max_batch);
-    bmax = std::max(bmax, h_batch_sizes[s]);
-  }
+  const int bmax = check_run(m, n_steps, slot0, h_batch_sizes);
+  if (bmax < 0) return bmax;
   if (!can_fuse(m) && (rc = need_grad(m, 1))) return rc;
-  pyz_mlp_full *f = full(m);
   hipStream_t st = as_stream(stream);
   BbbChain bbb_local{};
   if (bbb) {
@@ -1261,48 +1302,11 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
       if ((rc = set_ctl(v, 0, bbb->n_val, 0.0f, 0, 0, 0, st))) return rc;
     }
   }
-  // per-run tables (one padding entry: the last step prepares a slot nobody reads); batch sizes and learning
-  // rates share one device allocation
-  const size_t n_tab = (size_t)n_steps + 1;
-  if ((rc = ensure_run_tables(m, n_tab, 8, st))) return rc;
   const long long row_stride = m->max_batch;
-  bool first_batch_done = false;
-  if (n_steps <= PYZ_INLINE_TAB) {
-    // short run: the tables ride in the arguments of the launch that sets the first step's scalars
-    InlineTabs tabs{};
-    for (int s = 0; s < n_steps; ++s) {
-      tabs.bs[s] = h_batch_sizes[s];
-      tabs.lr[s] = h_lr[s];
-    }
-    tabs.bs[n_steps] = h_batch_sizes[n_steps - 1];
-    tabs.lr[n_steps] = h_lr[n_steps - 1];
-    tabs.n = n_steps + 1;
-    m->pend_on = false;
-    if (batch_ahead(m, d_row_idx)) {   // ... together with the first batch of the run
-      PYZ_LAUNCH(k_run_start, dim3(256), dim3(256), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride,
-                 (int)slot0, prep_args(m, d_x, d_row_idx, bmax, row_stride, 0));
-      first_batch_done = true;
-    } else {
-      PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0);
-    }
-  } else {
-    const unsigned slot = (unsigned)(f->x.tab_count & 1);
-    if (f->x.tab_count >= 2) PYZ_HIP(hipEventSynchronize(f->x.tab_ev[slot]));
-    ++f->x.tab_count;
-    int32_t *hb = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(f->x.tab_host) + slot * f->x.tab_host_cap);
-    float *hl = reinterpret_cast<float *>(hb + n_tab);
-    std::memcpy(hb, h_batch_sizes, sizeof(int32_t) * n_steps);
-    std::memcpy(hl, h_lr, sizeof(float) * n_steps);
-    hb[n_steps] = h_batch_sizes[n_steps - 1];
-    hl[n_steps] = h_lr[n_steps - 1];
-    PYZ_HIP(hipMemcpyAsync(m->tab_bs, hb, sizeof(int32_t) * n_tab, hipMemcpyHostToDevice, st));
-    PYZ_HIP(hipMemcpyAsync(m->tab_lr, hl, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
-    PYZ_HIP(hipEventRecord(f->x.tab_ev[slot], st));
-    if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], n0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
-  }
-
-  if (batch_ahead(m, d_row_idx) && !first_batch_done)   // the first batch of the run (every later one is assembled by the step before it)
-    PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, bmax, row_stride, 0), m->ctl);
+  // every step is launched for the largest batch of the call: the first batch is placed for its forward tiles too
+  if ((rc = upload_run_tables(m, h_batch_sizes, h_lr, n_steps, n0, slot0, nullptr, d_x, d_row_idx,
+                              batch_ahead(m, d_row_idx) ? bmax : 0, st)))
+    return rc;
 
   int s = 0;
   m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
@@ -1333,45 +1337,18 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
       mix((unsigned long long)bbb->n_val); mix((unsigned long long)(uintptr_t)bbb->val_losses);
       mix((unsigned long long)(uintptr_t)bbb->w2); mix((unsigned long long)(uintptr_t)bbb->rho); mix((unsigned long long)(uintptr_t)full(m)->x.part2);
     }
-    if (m->graph_key != key) {
-      drop_graphs(m);
-      m->graph_key = key;
-    }
+    m->graphs.rekey(key);
+    m->graphs.begin_call();
     while (s < n_steps) {
       const int len = std::min(G, n_steps - s);
-      int ci = 0;
-      if (len < G) {  // the remainder: its own graph, by exact length
-        ci = -1;
-        int free_slot = -1, lru = -1;
-        for (int c = 1; c < PYZ_GRAPH_CHUNKS; ++c) {
-          if (!m->graph_exec[c]) {
-            if (free_slot < 0) free_slot = c;
-            continue;
-          }
-          if (m->graph_len[c] == len) ci = c;
-          if (lru < 0 || m->graph_use[c] < m->graph_use[lru]) lru = c;
-        }
-        if (ci < 0) {
-          ci = free_slot >= 0 ? free_slot : lru;
-          if (m->graph_exec[ci]) (void)hipGraphExecDestroy(m->graph_exec[ci]);
-          if (m->graph[ci]) (void)hipGraphDestroy(m->graph[ci]);
-          m->graph_exec[ci] = nullptr;
-          m->graph[ci] = nullptr;
-        }
-      }
-      if (!m->graph_exec[ci]) {
-        PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+      const bool rest = len < G;   // the remainder: its own graph, by exact length in slots 1 ..; slot 0 holds the full chunk
+      rc = m->graphs.launch(len, 0, rest ? 1 : 0, rest ? PYZ_GRAPH_CHUNKS : 1, st, [&] {
         for (int k = 0; k < len; ++k)
           launch_sgld_step(m, d_theta, d_mean, d_sq_mean, d_x, d_y, d_row_idx, bmax, k & 1, true, row_stride, seed,
                            nullptr, d_losses, st, mode, swag, bbb, k == 0);
-        hipGraph_t gr = nullptr;
-        PYZ_HIP(hipStreamEndCapture(st, &gr));
-        m->graph[ci] = gr;
-        PYZ_HIP(hipGraphInstantiate(&m->graph_exec[ci], gr, nullptr, nullptr, 0));
-        m->graph_len[ci] = len;
-      }
-      m->graph_use[ci] = ++m->graph_clock;
-      PYZ_HIP(hipGraphLaunch(m->graph_exec[ci], st));
+        return PYZ_OK;
+      });
+      if (rc) return rc;
       s += len;
       m->run_graph_steps += len;
       ++m->run_graph_launches;
@@ -1474,44 +1451,12 @@ int pyz_sgld_chains_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_m
   int rc = sgld_chains_check(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_losses, n0);
   if (rc) return rc;
   if (!d_row_idx || !h_batch_sizes || !h_lr) return pyz_fail(PYZ_E_INVALID, "null pointer");
-  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "n_steps must be positive");
-  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "slot0 out of range");
-  for (int s = 0; s < n_steps; ++s)
-    if (h_batch_sizes[s] <= 0 || h_batch_sizes[s] > m->max_batch)
-      return pyz_fail(PYZ_E_SHAPE, "batch size %d of step %d outside [1, %d]", h_batch_sizes[s], s, m->max_batch);
+  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
   if ((rc = need_grad(m, n_chains))) return rc;
-  pyz_mlp_full *f = full(m);
   hipStream_t st = as_stream(stream);
-  // per-run tables (one padding entry: the last step prepares a slot nobody reads), as pyz_sgld_run sends them up
-  const size_t n_tab = (size_t)n_steps + 1;
-  if ((rc = ensure_run_tables(m, n_tab, 8, st))) return rc;
   const long long row_stride = m->max_batch;
-  if (n_steps <= PYZ_INLINE_TAB) {
-    InlineTabs tabs{};
-    for (int s = 0; s < n_steps; ++s) {
-      tabs.bs[s] = h_batch_sizes[s];
-      tabs.lr[s] = h_lr[s];
-    }
-    tabs.bs[n_steps] = h_batch_sizes[n_steps - 1];
-    tabs.lr[n_steps] = h_lr[n_steps - 1];
-    tabs.n = n_steps + 1;
-    m->pend_on = false;
-    PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0);
-  } else {
-    const unsigned slot = (unsigned)(f->x.tab_count & 1);
-    if (f->x.tab_count >= 2) PYZ_HIP(hipEventSynchronize(f->x.tab_ev[slot]));
-    ++f->x.tab_count;
-    int32_t *hb = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(f->x.tab_host) + slot * f->x.tab_host_cap);
-    float *hl = reinterpret_cast<float *>(hb + n_tab);
-    std::memcpy(hb, h_batch_sizes, sizeof(int32_t) * n_steps);
-    std::memcpy(hl, h_lr, sizeof(float) * n_steps);
-    hb[n_steps] = h_batch_sizes[n_steps - 1];
-    hl[n_steps] = h_lr[n_steps - 1];
-    PYZ_HIP(hipMemcpyAsync(m->tab_bs, hb, sizeof(int32_t) * n_tab, hipMemcpyHostToDevice, st));
-    PYZ_HIP(hipMemcpyAsync(m->tab_lr, hl, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
-    PYZ_HIP(hipEventRecord(f->x.tab_ev[slot], st));
-    if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], n0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
-  }
+  // the tables go up as pyz_sgld_run sends them; no batch is assembled ahead
+  if ((rc = upload_run_tables(m, h_batch_sizes, h_lr, n_steps, n0, slot0, nullptr, d_x, d_row_idx, 0, st))) return rc;
   m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
   for (int s = 0; s < n_steps; ++s) {
     launch_sgld_chains_step(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true,
@@ -1760,83 +1705,27 @@ static int adam_run_impl(pyz_mlp *m, AdamRunCfg &c, float *d_theta, const float 
   if (!can_fuse(m)) return pyz_fail(PYZ_E_INVALID, "the chained ADAM / VADAM / BSAM runs need a last layer of at most 32 units");
   int rc = check_loss_combo(m);
   if (rc) return rc;
-  if (n_steps <= 0) return pyz_fail(PYZ_E_INVALID, "n_steps must be positive");
-  if (slot0 < 0 || slot0 + n_steps > 0x7fffffff) return pyz_fail(PYZ_E_INVALID, "slot0 out of range");
+  if ((rc = check_run(m, n_steps, slot0, nullptr)) < 0) return rc;
   if (step0 < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
   if (!d_theta || !c.m || !c.v || !d_x || !d_y || !d_row_idx || !h_batch_sizes || !h_lr || !d_losses || (!c.bsam && !h_epochs))
     return pyz_fail(PYZ_E_INVALID, "null pointer");
   if (!(beta_1 >= 0.0 && beta_1 < 1.0) || !(beta_2 >= 0.0 && beta_2 < 1.0))
     return pyz_fail(PYZ_E_INVALID, "beta_1 = %g, beta_2 = %g: both must lie in [0, 1)", beta_1, beta_2);
   if (c.perturbs && !(c.c.num_data > 0.0f)) return pyz_fail(PYZ_E_INVALID, "num_data = %g must be positive", (double)c.c.num_data);
-  for (int s = 0; s < n_steps; ++s) {
-    if (h_batch_sizes[s] <= 0 || h_batch_sizes[s] > m->max_batch)
-      return pyz_fail(PYZ_E_SHAPE, "batch size %d of step %d outside [1, %d]", h_batch_sizes[s], s, m->max_batch);
-    if (!c.bsam && h_epochs[s] < 1) return pyz_fail(PYZ_E_INVALID, "epoch %lld of step %d < 1", (long long)h_epochs[s], s);
-  }
+  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes, c.bsam ? nullptr : h_epochs)) < 0) return rc;
   if (c.bsam && (rc = need_grad2(m, 1))) return rc;   // grad2 keeps the first pass's gradient
   pyz_mlp_full *f = full(m);
   hipStream_t st = as_stream(stream);
   static const int fuse_perturb = pyz_env_int("PYZ_ADAM_FUSE_PERTURB", 1);
   c.c.perturb = (c.perturbs && fuse_perturb) ? 1 : 0;
 
-  const size_t n_tab = (size_t)n_steps + 1;
-  if ((rc = ensure_run_tables(m, n_tab, c.bsam ? 8 : 16, st))) return rc;
-  if (!c.bsam && f->x.tab_bc_cap < m->tab_cap) {   // (as large as the other tables: its address is baked into the graphs too)
-    if (f->x.tab_bc) PYZ_HIP(hipFree(f->x.tab_bc));
-    f->x.tab_bc = nullptr;
-    f->x.tab_bc_cap = 0;
-    PYZ_HIP(hipMalloc((void **)&f->x.tab_bc, sizeof(float2) * (size_t)m->tab_cap));
-    f->x.tab_bc_cap = m->tab_cap;
-  }
-  c.c.tab_bc = c.bsam ? nullptr : f->x.tab_bc;
-  // 1 - beta^epoch of step s exactly as adam_scalars evaluates it for the eager step
-  auto bc_of = [&](int s) {
-    const AdamScal a = adam_scalars(0.0f, beta_1, beta_2, h_epochs[s], 0.0f, 0.0f);
-    return make_float2(a.bc1, a.bc2);
-  };
   const long long row_stride = m->max_batch;
-  const bool ahead = batch_ahead(m, d_row_idx);
-  m->pend_on = false;
-  if (n_steps <= PYZ_INLINE_TAB) {   // short run: the tables ride in the arguments of the launch that sets the first step's scalars
-    InlineTabs tabs{};
-    InlineBc ibc{};
-    for (int s = 0; s <= n_steps; ++s) {
-      const int ss = std::min(s, n_steps - 1);
-      tabs.bs[s] = h_batch_sizes[ss];
-      tabs.lr[s] = h_lr[ss];
-      if (!c.bsam) ibc.bc[s] = bc_of(ss);
-    }
-    tabs.n = n_steps + 1;
-    const long long row_off = slot0 * row_stride;
-    if (ahead) {   // ... together with the first batch of the run
-      const PrepArgs pa = prep_args(m, d_x, d_row_idx, h_batch_sizes[0], row_stride, 0);
-      if (c.bsam) PYZ_LAUNCH(k_run_start, dim3(256), dim3(256), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)step0, row_off, (int)slot0, pa);
-      else PYZ_LAUNCH(k_run_start_bc, dim3(256), dim3(256), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, f->x.tab_bc, (long long)step0, row_off, (int)slot0, pa);
-    } else {
-      if (c.bsam) PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)step0, row_off, (int)slot0);
-      else PYZ_LAUNCH(k_set_ctl_tabs_bc, dim3(1), dim3(64), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, f->x.tab_bc, (long long)step0, row_off, (int)slot0);
-    }
-  } else {
-    const unsigned slot = (unsigned)(f->x.tab_count & 1);
-    if (f->x.tab_count >= 2) PYZ_HIP(hipEventSynchronize(f->x.tab_ev[slot]));
-    ++f->x.tab_count;
-    int32_t *hb = reinterpret_cast<int32_t *>(static_cast<unsigned char *>(f->x.tab_host) + slot * f->x.tab_host_cap);
-    float *hl = reinterpret_cast<float *>(hb + n_tab);
-    float2 *hc = reinterpret_cast<float2 *>(hl + n_tab);   // (8 n_tab bytes in: aligned)
-    for (int s = 0; s <= n_steps; ++s) {
-      const int ss = std::min(s, n_steps - 1);
-      hb[s] = h_batch_sizes[ss];
-      hl[s] = h_lr[ss];
-      if (!c.bsam) hc[s] = bc_of(ss);
-    }
-    PYZ_HIP(hipMemcpyAsync(m->tab_bs, hb, sizeof(int32_t) * n_tab, hipMemcpyHostToDevice, st));
-    PYZ_HIP(hipMemcpyAsync(m->tab_lr, hl, sizeof(float) * n_tab, hipMemcpyHostToDevice, st));
-    if (!c.bsam) PYZ_HIP(hipMemcpyAsync(f->x.tab_bc, hc, sizeof(float2) * n_tab, hipMemcpyHostToDevice, st));
-    PYZ_HIP(hipEventRecord(f->x.tab_ev[slot], st));
-    if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], step0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
-    if (ahead)   // the first batch of the run (every later one is assembled by the step before it)
-      PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, h_batch_sizes[0], row_stride, 0), m->ctl);
-  }
+  const RunBc bc{beta_1, beta_2, h_epochs};
+  // each step is launched for its own batch size: the first batch is placed for the forward tiles of the first step
+  if ((rc = upload_run_tables(m, h_batch_sizes, h_lr, n_steps, step0, slot0, c.bsam ? nullptr : &bc, d_x, d_row_idx,
+                              batch_ahead(m, d_row_idx) ? h_batch_sizes[0] : 0, st)))
+    return rc;
+  c.c.tab_bc = c.bsam ? nullptr : f->x.tab_bc;
   // fused perturbation: only the first step of the call has nobody in front of it to perturb its weights
   if (c.c.perturb) {
     const unsigned pgrid = (unsigned)cdiv(cdiv(m->D, 4), 256);
@@ -1849,9 +1738,8 @@ static int adam_run_impl(pyz_mlp *m, AdamRunCfg &c, float *d_theta, const float 
   };
   int s = 0;
   m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
-  Extra &x = f->x;
-  x.ar_captures = 0;
-  const unsigned long long call_clock = x.ar_clock;   // graphs used after this stamp may still be in flight
+  PyzGraphCache<Extra::AR_GRAPHS> &graphs = f->x.adam_graphs;
+  graphs.begin_call();
   static const int G = std::min(128, std::max(2, pyz_env_int("PYZ_GRAPH_STEPS", 32) & ~1));   // even: the chunks of a stretch start on one StepCtl slot
   if (use_graph && st != nullptr && !pyz_probe().on) {
     // everything baked into the graphs goes into the key (but the batch sizes: they go into each graph's own signature)
@@ -1866,10 +1754,7 @@ static int adam_run_impl(pyz_mlp *m, AdamRunCfg &c, float *d_theta, const float 
     mix((unsigned long long)c.perturbs); mix((unsigned long long)c.c.perturb); mixf(c.c.lam); mixf(c.c.num_data);
     for (float v : {c.as.b1, c.as.c1, c.as.b2, c.as.c2, c.as.eps, c.as.decay}) mixf(v);
     for (float v : {c.bs.b1, c.bs.c1, c.bs.b2, c.bs.c2, c.bs.lam, c.bs.rho, c.bs.gam, c.bs.inv_n}) mixf(v);
-    if (x.ar_key != key) {
-      drop_adam_run_graphs(x);
-      x.ar_key = key;
-    }
+    graphs.rekey(key);
     while (s < n_steps) {
       // a graph holds steps of ONE batch size: chunks of G inside a stretch of equal batches, one graph for the stretch's
       // remainder -- so the ragged batch that ends an epoch is a graph of one step, and a run whose epochs do not line up
@@ -1878,36 +1763,11 @@ static int adam_run_impl(pyz_mlp *m, AdamRunCfg &c, float *d_theta, const float 
       while (s + stretch < n_steps && h_batch_sizes[s + stretch] == h_batch_sizes[s]) ++stretch;
       const int len = std::min(G, stretch);
       const unsigned long long sig = ((unsigned long long)h_batch_sizes[s] << 1) | (unsigned long long)(s & 1);
-      int ci = -1, free_slot = -1, lru = -1;
-      for (int k = 0; k < Extra::AR_GRAPHS; ++k) {
-        if (!x.ar_exec[k]) {
-          if (free_slot < 0) free_slot = k;
-          continue;
-        }
-        if (x.ar_len[k] == len && x.ar_sig[k] == sig) ci = k;
-        if (lru < 0 || x.ar_use[k] < x.ar_use[lru]) lru = k;
-      }
-      if (ci < 0) {
-        ci = free_slot >= 0 ? free_slot : lru;
-        if (x.ar_exec[ci]) {
-          if (x.ar_use[ci] > call_clock) PYZ_HIP(hipStreamSynchronize(st));   // launched by this call: let it finish first
-          (void)hipGraphExecDestroy(x.ar_exec[ci]);
-        }
-        if (x.ar_graph[ci]) (void)hipGraphDestroy(x.ar_graph[ci]);
-        x.ar_exec[ci] = nullptr;
-        x.ar_graph[ci] = nullptr;
-        PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+      rc = graphs.launch(len, sig, 0, Extra::AR_GRAPHS, st, [&] {
         for (int k = 0; k < len; ++k) step(s + k);
-        hipGraph_t gr = nullptr;
-        PYZ_HIP(hipStreamEndCapture(st, &gr));
-        x.ar_graph[ci] = gr;
-        PYZ_HIP(hipGraphInstantiate(&x.ar_exec[ci], gr, nullptr, nullptr, 0));
-        x.ar_len[ci] = len;
-        x.ar_sig[ci] = sig;
-        ++x.ar_captures;
-      }
-      x.ar_use[ci] = ++x.ar_clock;
-      PYZ_HIP(hipGraphLaunch(x.ar_exec[ci], st));
+        return PYZ_OK;
+      });
+      if (rc) return rc;
       s += len;
       m->run_graph_steps += len;
       ++m->run_graph_launches;
@@ -1940,7 +1800,7 @@ int pyz_adam_run(pyz_mlp *m, float *d_theta, float *d_m, float *d_v, const float
 
 int pyz_adam_run_info(const pyz_mlp *m, int32_t *h_captures) {
   if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
-  if (h_captures) *h_captures = static_cast<const pyz_mlp_full *>(m)->x.ar_captures;
+  if (h_captures) *h_captures = static_cast<const pyz_mlp_full *>(m)->x.adam_graphs.captures;
   return PYZ_OK;
 }
 
@@ -2147,19 +2007,11 @@ int pyz_hmc_step(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_
           PYZ_LAUNCH_CHECK();
           return PYZ_OK;
         }
-        if (!fm->x.hm_exec || fm->x.hm_key != key) {
-          if (fm->x.hm_exec) { (void)hipGraphExecDestroy(fm->x.hm_exec); fm->x.hm_exec = nullptr; }
-          if (fm->x.hm_graph) { (void)hipGraphDestroy(fm->x.hm_graph); fm->x.hm_graph = nullptr; }
-          PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        fm->x.hm_graphs.rekey(key);
+        return fm->x.hm_graphs.launch(1, 0, 0, 1, st, [&] {
           launch_all();
-          hipGraph_t gr = nullptr;
-          PYZ_HIP(hipStreamEndCapture(st, &gr));
-          fm->x.hm_graph = gr;
-          PYZ_HIP(hipGraphInstantiate(&fm->x.hm_exec, fm->x.hm_graph, nullptr, nullptr, 0));
-          fm->x.hm_key = key;
-        }
-        PYZ_HIP(hipGraphLaunch(fm->x.hm_exec, st));
-        return PYZ_OK;
+          return PYZ_OK;
+        });
       }
       if (lds > 64 * 1024)
         PYZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2348,7 +2200,7 @@ int pyz_hmc_run(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_y
     return PYZ_OK;
   };
   m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
-  x.hr_captures = 0;
+  x.hmc_run_graphs.begin_call();
   int s = 0;
   if ((rc = proposal(s))) return rc;
   ++s;
@@ -2361,49 +2213,16 @@ int pyz_hmc_run(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_y
     auto mix = [&](unsigned long long v) { key = (key ^ v) * 1099511628211ull; };
     mix((unsigned long long)(uintptr_t)x.hr_buf); mix((unsigned long long)(uintptr_t)ra.unif); mix((unsigned long long)m->max_p);
     mix((unsigned long long)m->D); mix((unsigned long long)G);
-    if (x.hr_key != key) {
-      drop_hmc_run_graphs(x);
-      x.hr_key = key;
-    }
+    x.hmc_run_graphs.rekey(key);
     while (s < n_steps) {
       const int len = std::min(G, n_steps - s);
-      int ci = 0;
-      if (len < G) {  // the remainder: its own graph, by exact length
-        ci = -1;
-        int free_slot = -1, lru = -1;
-        for (int c = 1; c < PYZ_GRAPH_CHUNKS; ++c) {
-          if (!x.hr_exec[c]) {
-            if (free_slot < 0) free_slot = c;
-            continue;
-          }
-          if (x.hr_len[c] == len) ci = c;
-          if (lru < 0 || x.hr_use[c] < x.hr_use[lru]) lru = c;
-        }
-        if (ci < 0) {
-          ci = free_slot >= 0 ? free_slot : lru;
-          if (x.hr_exec[ci]) (void)hipGraphExecDestroy(x.hr_exec[ci]);
-          if (x.hr_graph[ci]) (void)hipGraphDestroy(x.hr_graph[ci]);
-          x.hr_exec[ci] = nullptr;
-          x.hr_graph[ci] = nullptr;
-        }
-      }
-      if (!x.hr_exec[ci]) {
-        PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+      const bool rest = len < G;   // the remainder: its own graph, by exact length in slots 1 ..; slot 0 holds the full chunk
+      rc = x.hmc_run_graphs.launch(len, 0, rest ? 1 : 0, rest ? PYZ_GRAPH_CHUNKS : 1, st, [&] {
         int crc = PYZ_OK;
         for (int k = 0; k < len && !crc; ++k) crc = proposal(s + k);   // (step and burning ride in HmcCall: the graph fits any position)
-        hipGraph_t gr = nullptr;
-        const hipError_t ce = hipStreamEndCapture(st, &gr);
-        if (crc || ce != hipSuccess) {
-          if (gr) (void)hipGraphDestroy(gr);
-          return crc ? crc : pyz_fail(PYZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        }
-        x.hr_graph[ci] = gr;
-        PYZ_HIP(hipGraphInstantiate(&x.hr_exec[ci], gr, nullptr, nullptr, 0));
-        x.hr_len[ci] = len;
-        ++x.hr_captures;
-      }
-      x.hr_use[ci] = ++x.hr_clock;
-      PYZ_HIP(hipGraphLaunch(x.hr_exec[ci], st));
+        return crc;
+      });
+      if (rc) return rc;
       s += len;
       m->run_graph_steps += len;
       ++m->run_graph_launches;
@@ -2419,7 +2238,7 @@ int pyz_hmc_run(pyz_mlp *m, float *d_q, int P, const float *d_x, const void *d_y
 
 int pyz_hmc_run_info(const pyz_mlp *m, int32_t *h_captures) {
   if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
-  if (h_captures) *h_captures = static_cast<const pyz_mlp_full *>(m)->x.hr_captures;
+  if (h_captures) *h_captures = static_cast<const pyz_mlp_full *>(m)->x.hmc_run_graphs.captures;
   return PYZ_OK;
 }
 

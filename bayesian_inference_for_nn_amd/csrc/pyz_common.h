@@ -165,6 +165,77 @@ inline PyzProbe &pyz_probe() {
     }                                                                                                            \
   } while (0)
 
+// ---------------------------------------------------------------- captured graphs of the device-resident runs
+// N slots, each a graph of `len` steps captured for `sig` (whatever else tells two graphs of one length apart).  Everything
+// baked into ALL of them is hashed into `key` by the caller: rekey() drops every graph when it changes.
+template <int N>
+struct PyzGraphCache {
+  hipGraph_t graph[N] = {};
+  hipGraphExec_t exec[N] = {};
+  int len[N] = {};
+  unsigned long long sig[N] = {}, use[N] = {};   // use: last launch of the slot on `clock` (eviction order)
+  unsigned long long clock = 0, key = 0;
+  unsigned long long call_clock = 0;             // the clock when the current call began: slots used later may be in flight
+  int captures = 0;                              // graphs captured since begin_call()
+
+  void drop_slot(int c) {
+    if (exec[c]) (void)hipGraphExecDestroy(exec[c]);
+    if (graph[c]) (void)hipGraphDestroy(graph[c]);
+    exec[c] = nullptr;
+    graph[c] = nullptr;
+    len[c] = 0;
+  }
+  void drop() {
+    for (int c = 0; c < N; ++c) drop_slot(c);
+  }
+  void rekey(unsigned long long k) {
+    if (key != k) {
+      drop();
+      key = k;
+    }
+  }
+  void begin_call() {
+    captures = 0;
+    call_clock = clock;
+  }
+  // Launches the graph of `n` steps with signature `s` out of slots [lo, hi).  None there: steps() enqueues them on st (and
+  // returns a pyz code) inside a capture, into a free slot, else in place of the least recently used one.  A capture that
+  // was begun is always ended.
+  template <class Steps>
+  int launch(int n, unsigned long long s, int lo, int hi, hipStream_t st, Steps &&steps) {
+    int ci = -1, free_slot = -1, lru = -1;
+    for (int c = lo; c < hi; ++c) {
+      if (!exec[c]) {
+        if (free_slot < 0) free_slot = c;
+        continue;
+      }
+      if (len[c] == n && sig[c] == s) ci = c;
+      if (lru < 0 || use[c] < use[lru]) lru = c;
+    }
+    if (ci < 0) {
+      ci = free_slot >= 0 ? free_slot : lru;
+      if (exec[ci] && use[ci] > call_clock) PYZ_HIP(hipStreamSynchronize(st));   // launched by this call: let it finish first
+      drop_slot(ci);
+      PYZ_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+      const int rc = steps();
+      hipGraph_t gr = nullptr;
+      const hipError_t ce = hipStreamEndCapture(st, &gr);
+      if (rc || ce != hipSuccess) {
+        if (gr) (void)hipGraphDestroy(gr);
+        return rc ? rc : pyz_fail(PYZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+      }
+      graph[ci] = gr;
+      PYZ_HIP(hipGraphInstantiate(&exec[ci], gr, nullptr, nullptr, 0));
+      len[ci] = n;
+      sig[ci] = s;
+      ++captures;
+    }
+    use[ci] = ++clock;
+    PYZ_HIP(hipGraphLaunch(exec[ci], st));
+    return PYZ_OK;
+  }
+};
+
 // ---------------------------------------------------------------- the plan
 #define PYZ_GRAPH_CHUNKS 8  // captured step graphs: slot 0 = G steps, the others = remainders by exact length (LRU)
 struct pyz_mlp {
@@ -194,12 +265,8 @@ struct pyz_mlp {
   float *tab_lr = nullptr;
   int tab_cap = 0;
   float *h_pinned = nullptr;                 // pinned host staging
-  // device-resident runs: one captured graph per chunk length (everything baked into them goes into graph_key)
-  hipGraph_t graph[PYZ_GRAPH_CHUNKS] = {nullptr};
-  hipGraphExec_t graph_exec[PYZ_GRAPH_CHUNKS] = {nullptr};
-  int graph_len[PYZ_GRAPH_CHUNKS] = {0};
-  unsigned long long graph_use[PYZ_GRAPH_CHUNKS] = {0}, graph_clock = 0;   // last use of a slot (eviction order)
-  unsigned long long graph_key = 0;
+  // device-resident runs: one captured graph per chunk length (everything baked into them goes into the cache's key)
+  PyzGraphCache<PYZ_GRAPH_CHUNKS> graphs;
   // what the last pyz_*_run call did: steps inside replayed graphs, eager steps, graph launches
   int run_graph_steps = 0, run_eager_steps = 0, run_graph_launches = 0;
   int *nonfinite = nullptr;                  // device counter: steps whose loss was NaN / Inf (pyz_check_finite)

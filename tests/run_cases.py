@@ -5,8 +5,9 @@ A run adds to the step: step scalars that live on the device and ping-pong betwe
 per-run tables (inline up to 32 steps, else through pinned staging buffers), batches assembled one step ahead by the idle
 workgroups of the weight-gradient launch (pyz_prep_rows, pyz_copy_rows), graphs of 32 steps and a remainder graph by exact
 length, SWAG's deviation row from the step count, BBB's next-step sample in the epilogue and its gated validation forward.
-This module restates the host rules of sgld_run_impl (`table_transport`, `batch_ahead`, `first_batch_launch`,
-`graph_chunks`, `prep_partition`, `expected_run_launches`), names the cells of the coverage table (`CELLS`,
+This module restates the host rules of sgld_run_impl and of what it shares with the other run entries: upload_run_tables
+(`table_transport`, `first_batch_launch`) and the graph cache PyzGraphCache of pyz_common.h (`graph_chunks`); beside them
+`batch_ahead`, `prep_partition` and `expected_run_launches`.  It names the cells of the coverage table (`CELLS`,
 `reached_cells`, `book_cells`), lists cases that reach every cell with every mode they apply to, builds their data
 (step_cases.step_data and a row table whose entries behind a step's batch are other valid rows), restates a run as a chain
 of step_cases.ref_step (`ref_run_step`: learning rate and batch of step i, count n0 + i, row slot slot0 + i, the SWAG row,
@@ -41,7 +42,7 @@ LR_FACTORS = (1.0, 0.75, 0.875, 0.5, 0.625, 0.375)   # learning rate of step i o
 
 
 def table_transport(n_steps: int) -> str:
-    """sgld_run_impl: `if (n_steps <= PYZ_INLINE_TAB)` the tables ride in k_run_start / k_set_ctl_tabs, else they go up
+    """upload_run_tables: `if (n_steps <= PYZ_INLINE_TAB)` the tables ride in k_run_start / k_set_ctl_tabs, else they go up
     through one of the two pinned staging buffers."""
     return "inline" if n_steps <= INLINE_TAB else "pinned"
 
@@ -261,8 +262,8 @@ def _norm(name: str) -> str:
 
 def expected_run_launches(case: RunCase, mode: str, n_steps: int, n_val: int = 0) -> list:
     """Every launch of one eager-chained run (use_graph off, or inside KernelProbe) in order, spaces removed.
-    sgld_run_impl: [k_set_ctl of the validation plan], then k_run_start | k_set_ctl_tabs (inline tables) or k_set_ctl
-    [+ k_prep_batch] (pinned tables); per step launch_sgld_step at grid batch bmax: BBB's k_bbb_sample on the first step
+    sgld_run_impl: [k_set_ctl of the validation plan], then upload_run_tables: k_run_start | k_set_ctl_tabs (inline
+    tables) or k_set_ctl [+ k_prep_batch] (pinned tables); per step launch_sgld_step at grid batch bmax: BBB's k_bbb_sample on the first step
     only (later weights come out of the epilogue before), hidden forwards, head, hidden data gradients, k_wgrad_all<S>;
     BBB with validation: hidden forwards, head and k_loss_finalize_gated of the validation plan, in every step; unfused
     SGLD: every forward, the loss kernel, data / weight gradients per layer from the last, k_sgld_update."""

@@ -1,5 +1,5 @@
 """Every device-resident SGD, SWAG, SGLD and BBB run path (pyz_sgd_run, pyz_swag_run, pyz_sgld_run, pyz_bbb_run: all four are
-sgld_run_impl) against the float64 oracle and against the eager steps (tests/run_cases.py lists the cases and cells).
+sgld_run_impl over the shared upload_run_tables and PyzGraphCache) against the float64 oracle and against the eager steps (tests/run_cases.py lists the cases and cells).
 
 Oracle tier: a short ragged run of six steps, launched for its largest batch while later steps have 1, an odd number or fewer
 than 2 S rows.  Every prefix of it runs from the same start, so the state after prefix i is the state before step i and

@@ -1,6 +1,7 @@
 """The run case table (tests/run_cases.py) against the library's source and the oracle modules, on the CPU.
 
-The host rules of sgld_run_impl restated in run_cases (table transport, batch-ahead, first-batch launch, graph chunks, the
+The host rules of sgld_run_impl, of the table upload it shares with the other run entries (upload_run_tables) and of the
+graph cache (PyzGraphCache) restated in run_cases (table transport, batch-ahead, first-batch launch, graph chunks, the
 partition of pyz_prep_rows, the chain rules of pyz_prepare_next, the SWAG row, the BBB gate) are pinned to the text of
 pyz_api.hip, pyz_fused.h, pyz_kernels.h and pyz_common.h; the cells the cases and bookkeeping runs reach are compared with
 the coverage table name by name; pyz_prep_rows' restatement must hand every row of every batch size to exactly one worker;
@@ -8,6 +9,7 @@ the run reference (a chain of step_cases.ref_step) is held bit-equal to oracle.s
 run in float64; and the comparison the GPU matrix uses is run with the float32 run reference in place of the device (it
 must pass) and with every wrong run reference (each must fail on every case it applies to)."""
 
+import os
 import re
 
 import numpy as np
@@ -22,7 +24,7 @@ from oracle import sgd as o_sgd
 from oracle import sgld as o_sgld
 from oracle import swag as o_swag
 from run_cases import BOOKS, CASES, CELLS, MODES, RUN_MUTATIONS, compare_run_step, ref_run_step, run_data
-from test_dense_dispatch_table import env_default, function_body, squash, src
+from test_dense_dispatch_table import CSRC, env_default, function_body, squash, src
 
 _DATA = {}
 
@@ -45,24 +47,39 @@ def test_constants_and_conditions_match_the_source():
         assert re.search(r'static const int \w+ =[^;]*pyz_env_int\("%s"' % name, api), name
     assert set(rc.ENV_FORBIDDEN) >= {"PYZ_GRAPH_STEPS", "PYZ_BATCH_AHEAD", "PYZ_BBB_FUSE_SAMPLE", "PYZ_FWD_KSPLIT"}
     run = function_body(api, "static int sgld_run_impl(")
-    # table transport and the first batch
-    assert "if (n_steps <= PYZ_INLINE_TAB) {" in run
-    inline, pinned = run[run.index("if (n_steps <= PYZ_INLINE_TAB) {"):].split("\n  } else {\n", 1)
-    assert inline.index("if (batch_ahead(m, d_row_idx)) {") < inline.index("PYZ_LAUNCH(k_run_start, dim3(256), dim3(256)") \
-        < inline.index("first_batch_done = true;") < inline.index("PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64)")
-    assert "slot0 * row_stride,\n                 (int)slot0, prep_args(m, d_x, d_row_idx, bmax, row_stride, 0));" in inline
+    up = function_body(api, "static int upload_run_tables(")
+    cache = function_body(common, "struct PyzGraphCache {")
+    # table transport and the first batch: the upload every run entry shares, asked by sgld_run_impl for its largest batch
+    assert "if ((rc = upload_run_tables(m, h_batch_sizes, h_lr, n_steps, n0, slot0, nullptr, d_x, d_row_idx,\n" \
+           "                              batch_ahead(m, d_row_idx) ? bmax : 0, st)))" in run
+    assert "if (n_steps <= PYZ_INLINE_TAB) {" in up
+    inline, pinned = up[up.index("if (n_steps <= PYZ_INLINE_TAB) {"):].split("\n    return PYZ_OK;\n  }\n", 1)
+    assert inline.index("if (ahead_batch) {") < inline.index("const PrepArgs pa = prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0);") \
+        < inline.index("PYZ_LAUNCH(k_run_start, dim3(256), dim3(256)") < inline.index("\n    } else {\n") \
+        < inline.index("PYZ_LAUNCH(k_set_ctl_tabs, dim3(1), dim3(64)")
+    assert "m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0, pa);" in inline and "k_prep_batch" not in inline
     assert "set_ctl(m, 0, h_batch_sizes[0], h_lr[0], n0, slot0 * row_stride, 0, st, (int)slot0, n_steps)" in pinned
-    assert "if (batch_ahead(m, d_row_idx) && !first_batch_done)" in pinned
-    assert "PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, bmax, row_stride, 0), m->ctl);" in pinned
-    assert "const long long row_stride = m->max_batch;" in run
+    assert pinned.index("set_ctl(m, 0, h_batch_sizes[0]") < pinned.index("  if (ahead_batch)   //") < pinned.index("PYZ_LAUNCH(k_prep_batch,")
+    assert "PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0), m->ctl);" in pinned
+    assert "const long long row_stride = m->max_batch;" in run and "const long long row_stride = m->max_batch;" in up
     # the padding entry repeats the last step's
-    assert "tabs.bs[n_steps] = h_batch_sizes[n_steps - 1];" in run and "hb[n_steps] = h_batch_sizes[n_steps - 1];" in run
-    # graphs: chunks of G, the remainder by exact length in slots 1 .., least recently used one replaced
+    assert "tabs.bs[n_steps] = h_batch_sizes[n_steps - 1];" in inline and "hb[n_steps] = h_batch_sizes[n_steps - 1];" in pinned
+    assert "tabs.lr[n_steps] = h_lr[n_steps - 1];" in inline and "hl[n_steps] = h_lr[n_steps - 1];" in pinned
+    # graphs: chunks of G in slot 0, the remainder by exact length in slots 1 .., a free slot before the least recently used one
     assert 'static const int G = std::min(128, std::max(2, pyz_env_int("PYZ_GRAPH_STEPS", 32) & ~1));' in run
     assert "if (use_graph && st != nullptr && !pyz_probe().on) {" in run
-    assert "const int len = std::min(G, n_steps - s);" in run and "if (len < G) {" in run
-    assert "for (int c = 1; c < PYZ_GRAPH_CHUNKS; ++c) {" in run and "if (m->graph_len[c] == len) ci = c;" in run
-    assert "if (lru < 0 || m->graph_use[c] < m->graph_use[lru]) lru = c;" in run and "ci = free_slot >= 0 ? free_slot : lru;" in run
+    assert "const int len = std::min(G, n_steps - s);" in run and "const bool rest = len < G;" in run
+    assert "rc = m->graphs.launch(len, 0, rest ? 1 : 0, rest ? PYZ_GRAPH_CHUNKS : 1, st, [&] {" in run
+    assert "PyzGraphCache<PYZ_GRAPH_CHUNKS> graphs;" in function_body(common, "struct pyz_mlp {")
+    assert "for (int c = lo; c < hi; ++c) {\n      if (!exec[c]) {\n        if (free_slot < 0) free_slot = c;\n        continue;\n      }\n" in cache
+    assert "if (len[c] == n && sig[c] == s) ci = c;" in cache
+    assert "if (lru < 0 || use[c] < use[lru]) lru = c;" in cache and "ci = free_slot >= 0 ? free_slot : lru;" in cache
+    assert "use[ci] = ++clock;" in cache
+    # one cache type: no run entry keeps slot arrays of its own
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".h", ".hip")):
+            for old in ("ar_exec", "hr_exec", "graph_exec["):
+                assert old not in src(name), (name, old)
     # every step is launched for the largest batch of the call, on StepCtl slot k & 1, the first flagged
     assert "launch_sgld_step(m, d_theta, d_mean, d_sq_mean, d_x, d_y, d_row_idx, bmax, k & 1, true, row_stride, seed,\n" \
            "                           nullptr, d_losses, st, mode, swag, bbb, k == 0);" in run
