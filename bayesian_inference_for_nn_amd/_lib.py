@@ -80,6 +80,8 @@ SIGNATURES = {
     "pyz_predict_moments": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
     "pyz_input_grad": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, _f, _p, _f, _p, _p, _p]),
     "pyz_sample_normal_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _u64, _u32, _u32, _p]),
+    "pyz_sample_lowrank_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _f, _u64, _u32, _u32, _p]),
+    "pyz_gather_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p]),
     "pyz_fill_normal": (C.c_int, [_p, _i64, _u64, _u32, _u32, _f, _f, _p]),
     "pyz_debug_stamps": (C.c_int, [C.POINTER(C.c_uint64), _i64]),
     "pyz_debug_mfma_f64_layout": (C.c_int, [C.POINTER(C.c_int32)]),
@@ -93,6 +95,7 @@ SIGNATURES = {
 }
 
 E_NAN = -6
+LOWRANK_MAX_K = 256       # PYZ_LOWRANK_MAX_K
 
 
 def header_version() -> int:

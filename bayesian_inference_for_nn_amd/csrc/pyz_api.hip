@@ -2762,6 +2762,34 @@ int pyz_sample_normal_rows(float *d_out, int64_t n_rows, int64_t row_stride, int
   return PYZ_OK;
 }
 
+int pyz_sample_lowrank_rows(float *d_out, int64_t n_rows, int64_t row_stride, int64_t col0, int64_t len, const float *d_mean,
+                            const float *d_diag, const float *d_dev, int k, float factor, uint64_t seed, uint32_t stream_id,
+                            uint32_t first_draw, void *stream) {
+  if (!d_out || !d_mean || !d_diag || !d_dev) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (n_rows <= 0 || n_rows > 65535 || len <= 0 || col0 < 0 || col0 + len > row_stride)
+    return pyz_fail(PYZ_E_INVALID, "bad draw count / column range");
+  if (k < 1 || k > PYZ_LOWRANK_MAX_K)
+    return pyz_fail(PYZ_E_INVALID, "k %d outside [1, %d] (PYZ_LOWRANK_MAX_K)", k, PYZ_LOWRANK_MAX_K);
+  const int vec_in = aligned16(d_mean) && aligned16(d_diag) && aligned16(d_dev) && (len % 4 == 0 || k == 1) ? 1 : 0;
+  PYZ_LAUNCH(k_sample_lowrank_rows, dim3(cdiv(len, PYZ_LOWRANK_TILE), cdiv(n_rows, PYZ_LOWRANK_ROWS)), dim3(256), 0,
+             as_stream(stream), d_out, (int)n_rows, (long long)row_stride, (long long)col0, (long long)len, d_mean, d_diag, d_dev,
+             k, factor, vec_in, seed, stream_id, first_draw);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_gather_rows(float *d_out, int64_t n_rows, int64_t row_stride, int64_t col0, int64_t len, const float *d_bank,
+                    int64_t n_bank, const int32_t *d_idx, void *stream) {
+  if (!d_out || !d_bank || !d_idx) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (n_rows <= 0 || n_rows > 65535 || len <= 0 || col0 < 0 || col0 + len > row_stride)
+    return pyz_fail(PYZ_E_INVALID, "bad row count / column range");
+  if (n_bank < 1) return pyz_fail(PYZ_E_INVALID, "the bank must hold at least one row");
+  PYZ_LAUNCH(k_gather_rows, dim3(cdiv(cdiv(len, 4), 256), (unsigned)n_rows), dim3(256), 0, as_stream(stream), d_out,
+             (long long)row_stride, (long long)col0, (long long)len, d_bank, (long long)n_bank, d_idx);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
 int pyz_fill_normal(float *d_out, int64_t n, uint64_t seed, uint32_t stream_id, uint32_t step, float mean, float std,
                     void *stream) {
   if (!d_out || n <= 0) return pyz_fail(PYZ_E_INVALID, "bad output buffer");

@@ -2350,6 +2350,139 @@ __global__ void k_sample_normal_rows(float *out, long long row_stride, long long
     if (e0 + j < len) o[e0 + j] = loc[e0 + j] + scale[e0 + j] * z[j];
 }
 
+// four consecutive floats to p, as wide as p's alignment allows (p is the same for a whole row, so the branch is
+// uniform; rows of an (n, D) matrix with D % 4 == 2 alternate between the 16-byte and the 8-byte form)
+__device__ __forceinline__ void pyz_store4(float *p, float a, float b, float c, float d) {
+  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+  if ((u & 15u) == 0) {
+    *reinterpret_cast<float4 *>(p) = make_float4(a, b, c, d);
+  } else if ((u & 7u) == 0) {
+    *reinterpret_cast<float2 *>(p) = make_float2(a, b);
+    *reinterpret_cast<float2 *>(p + 2) = make_float2(c, d);
+  } else {
+    p[0] = a;
+    p[1] = b;
+    p[2] = c;
+    p[3] = d;
+  }
+}
+
+// n_rows independent draws of SWAG's posterior (MultivariateNormalDiagPlusLowRank.py:32-41) into columns
+// [col0, col0 + len) of a row-major (n_rows, row_stride) matrix:
+//   out[r][col0 + e] = mean[e] + diag[e] z1(r, e) + factor * sum_c dev[c][e] z2(r, c),   dev (k, len) row-major,
+// z1(r, e) = element e and z2(r, c) = element 4 ceil(len / 4) + c of the Philox stream (seed, stream, step = first_draw + r)
+// (pyz_rng.h).  The arithmetic of one element, the same for every blocking of rows and columns over workgroups:
+//   s = 0;  s = fmaf(dev[c][e], z2(r, c), s) for c = 0, 1, ..., k - 1;  out = fmaf(factor, s, fmaf(diag[e], z1, mean[e])).
+// A workgroup owns PYZ_LOWRANK_TILE columns x PYZ_LOWRANK_ROWS rows: its k x rows values z2 are drawn once (pyz_normal1)
+// into LDS, a thread keeps the sums of its four columns for every row in registers, so a tile's slab of dev is read
+// once per row block and not once per row.  16-byte loads of mean / diag / dev where vec_in says their rows are 16-byte
+// aligned (the host: pointers aligned, len % 4 == 0 or k == 1); 16- or 8-byte stores by each row's own alignment; the
+// last, partial group of four columns and unaligned inputs take the scalar path.
+#ifndef PYZ_LOWRANK_ROWS
+#define PYZ_LOWRANK_ROWS 8
+#endif
+#define PYZ_LOWRANK_TILE 1024   // 256 threads x 4 columns
+__global__ __launch_bounds__(256) void k_sample_lowrank_rows(float *out, int n_rows, long long row_stride, long long col0,
+                                                             long long len, const float *mean, const float *diag,
+                                                             const float *dev, int k, float factor, int vec_in, uint64_t seed,
+                                                             uint32_t stream, uint32_t first_draw) {
+  constexpr int R = PYZ_LOWRANK_ROWS;
+  __shared__ __attribute__((aligned(16))) float z2s[PYZ_LOWRANK_MAX_K * R];   // [c][row of the block]
+  const int r0 = blockIdx.y * R;
+  const int nr = min(R, n_rows - r0);                                          // >= 1: the grid is cdiv(n_rows, R)
+  const uint64_t zbase = 4ull * (uint64_t)((len + 3) / 4);
+  for (int i = threadIdx.x; i < k * R; i += 256) {
+    const int c = i / R, j = i % R;
+    z2s[i] = j < nr ? pyz_normal1(seed, stream, first_draw + (uint32_t)(r0 + j), zbase + (uint64_t)c) : 0.0f;
+  }
+  __syncthreads();
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long e0 = 4 * t;
+  if (e0 >= len) return;
+  const int nq = (int)min(4ll, len - e0);
+  float s[R][4], m[4], d[4];
+#pragma unroll
+  for (int j = 0; j < R; ++j) s[j][0] = s[j][1] = s[j][2] = s[j][3] = 0.0f;
+  if (nq == 4 && vec_in) {
+    const float4 mv = *reinterpret_cast<const float4 *>(mean + e0), dv = *reinterpret_cast<const float4 *>(diag + e0);
+    m[0] = mv.x, m[1] = mv.y, m[2] = mv.z, m[3] = mv.w;
+    d[0] = dv.x, d[1] = dv.y, d[2] = dv.z, d[3] = dv.w;
+    const float *dp = dev + e0;
+#pragma unroll 4
+    for (int c = 0; c < k; ++c) {
+      const float4 v = *reinterpret_cast<const float4 *>(dp + (long long)c * len);
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const float z = z2s[c * R + j];
+        s[j][0] = fmaf(v.x, z, s[j][0]);
+        s[j][1] = fmaf(v.y, z, s[j][1]);
+        s[j][2] = fmaf(v.z, z, s[j][2]);
+        s[j][3] = fmaf(v.w, z, s[j][3]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      m[q] = q < nq ? mean[e0 + q] : 0.0f;
+      d[q] = q < nq ? diag[e0 + q] : 0.0f;
+    }
+    for (int c = 0; c < k; ++c) {
+      const float *dp = dev + (long long)c * len + e0;
+      float v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = q < nq ? dp[q] : 0.0f;
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const float z = z2s[c * R + j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[j][q] = fmaf(v[q], z, s[j][q]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    if (j >= nr) break;
+    const float4 zq = pyz_normal4(seed, stream, first_draw + (uint32_t)(r0 + j), (uint64_t)t);
+    const float z1[4] = {zq.x, zq.y, zq.z, zq.w};
+    float o[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = fmaf(factor, s[j][q], fmaf(d[q], z1[q], m[q]));
+    float *p = out + (long long)(r0 + j) * row_stride + col0 + e0;
+    if (nq == 4) {
+      pyz_store4(p, o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        if (q < nq) p[q] = o[q];
+    }
+  }
+}
+
+// out[r][col0 + e] = bank[idx[r]][e]: n_rows rows of the (n_bank, len) row-major matrix `bank` picked by the device
+// indices idx (int32) into columns [col0, col0 + len) of a row-major (n_rows, row_stride) matrix (Sampled.sample_n,
+// Sampled.py:29-32, with the stored samples kept on the device).  A row whose index is outside [0, n_bank) is left as it
+// is and reads nothing.  16-byte loads / 16- or 8-byte stores where the source / destination row is aligned for them.
+__global__ __launch_bounds__(256) void k_gather_rows(float *out, long long row_stride, long long col0, long long len,
+                                                     const float *bank, long long n_bank, const int32_t *idx) {
+  const long long e0 = 4 * ((long long)blockIdx.x * 256 + threadIdx.x);
+  if (e0 >= len) return;
+  const int r = blockIdx.y;
+  const long long b = idx[r];
+  if (b < 0 || b >= n_bank) return;
+  const float *src = bank + b * len + e0;
+  float *p = out + (long long)r * row_stride + col0 + e0;
+  if (e0 + 4 <= len) {
+    float4 v;
+    if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0)
+      v = *reinterpret_cast<const float4 *>(src);
+    else
+      v = make_float4(src[0], src[1], src[2], src[3]);
+    pyz_store4(p, v.x, v.y, v.z, v.w);
+  } else {
+    for (int q = 0; q < (int)(len - e0); ++q) p[q] = src[q];
+  }
+}
+
 // model output for pyz_mlp_forward: softmax (if any) applied, no NaN scrubbing
 __global__ void k_forward_finish(const float *last, long long pstride, int C, int softmax, int n, float *out) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;

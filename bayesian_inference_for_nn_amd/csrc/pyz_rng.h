@@ -16,9 +16,14 @@
 #define PYZ_STREAM_BBB 1u
 #define PYZ_STREAM_HMC 2u   // + chain index in the high bits: stream = 2 + 16 * chain
 #define PYZ_STREAM_INIT 3u
-#define PYZ_STREAM_PREDICT 4u
+#define PYZ_STREAM_PREDICT 4u  // weight draws of the read-outs, step = the draw's counter (tfd.take_device_draws); see below
 #define PYZ_STREAM_VADAM 5u  // VADAM weight perturbation (VADAM.py:59-65), step = the optimizer step
 #define PYZ_STREAM_BSAM 6u   // BSAM weight perturbation (BSAM.py:63-68), step = the optimizer step
+// PYZ_STREAM_PREDICT, one draw (step) of a distribution over len elements:
+//   k_sample_normal_rows    z(e)  = element e, e < len
+//   k_sample_lowrank_rows   z1(e) = element e, e < len;  z2(c) = element 4 * ceil(len / 4) + c, c < k
+// z1 ends inside counter idx4 = ceil(len / 4) - 1 and z2 starts with counter idx4 = ceil(len / 4): the two never share a
+// counter, whatever len % 4 is.
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;

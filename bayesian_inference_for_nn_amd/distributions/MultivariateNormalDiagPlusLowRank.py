@@ -27,6 +27,27 @@ class MultivariateNormalDiagPlusLowRank(Distribution):
         z2 = tfd._rng.standard_normal((n, k), dtype=np.float32)
         return (self._mean[None, :] + z1 + (z2 @ self._D.T) * np.float32(sqrt(1 / (2 * (k - 1))))).astype(np.float32)
 
+    def sample_n_device(self, n: int, out, col0: int) -> bool:
+        """n draws into columns [col0, col0 + size) of the CUDA matrix `out`, generated on the device from the Philox
+        stream of tfd.seed (k_sample_lowrank_rows); True when done.  False (the caller draws on the host with
+        ``sample_n``) with PYZ_SAMPLE_DEVICE=0, for more than PYZ_LOWRANK_MAX_K deviation columns and for n outside 1 .. 65535."""
+        if os.environ.get("PYZ_SAMPLE_DEVICE", "1") == "0":
+            return False
+        k = self._D.shape[1]
+        factor = sqrt(1 / (2 * (k - 1)))               # (k = 1: ZeroDivisionError, k = 0: ValueError, as in sample_n)
+        from .._lib import LOWRANK_MAX_K
+        if k > LOWRANK_MAX_K or not 1 <= n <= 65535:   # (one launch takes at most that many rows)
+            return False
+        import torch
+        from .. import engine
+        if getattr(self, "_dev", None) is None:
+            diag = np.array(np.broadcast_to(self._diag, self._mean.shape))
+            self._dev = (torch.as_tensor(self._mean).cuda(), torch.as_tensor(diag).cuda(),
+                         torch.as_tensor(np.ascontiguousarray(self._D.T)).cuda())      # (k, size): row c = column c of D
+        engine.sample_lowrank_rows(out, col0, self._dev[0], self._dev[1], self._dev[2], factor, tfd._dev_seed,
+                                   tfd.take_device_draws(n))
+        return True
+
     def sample(self):
         return self.sample_n(1)[0]
 

@@ -42,6 +42,26 @@ class Sampled(Distribution):
     def sample_n(self, n: int):
         return np.stack([self.sample() for _ in range(n)])
 
+    def sample_n_device(self, n: int, out, col0: int) -> bool:
+        """n draws into columns [col0, col0 + size) of the CUDA matrix `out`: the indices are drawn on the host exactly as
+        ``sample_n`` draws them (n calls of ``sample_index``), the rows are gathered on the device from a (n_samples, size)
+        float32 copy of the samples that is uploaded on first use and kept (k_gather_rows); True when done.  False (the
+        caller draws on the host with ``sample_n``) with PYZ_SAMPLE_DEVICE=0 and when the copy would be larger than
+        PYZ_SAMPLED_BANK_MAX bytes (default 2^33: a guard against a surprising allocation, not a tuned number)."""
+        if os.environ.get("PYZ_SAMPLE_DEVICE", "1") == "0":
+            return False
+        if 4 * self._n_samples * self._size > int(os.environ.get("PYZ_SAMPLED_BANK_MAX", 1 << 33)):
+            return False
+        if not 1 <= n <= 65535:                        # (one launch takes at most that many rows)
+            return False
+        import torch
+        from .. import engine
+        idx = [self.sample_index() for _ in range(n)]
+        if getattr(self, "_bank", None) is None:
+            self._bank = torch.as_tensor(np.stack(self._samples)).cuda()
+        engine.gather_rows(out, col0, self._bank, idx)
+        return True
+
     def store(self, path: str):
         """info.json + samples/sample<i>.tf, each sample a serialized TensorProto: what tf.io.serialize_tensor /
         tf.io.write_file leave there in the reference (Sampled.py:34-48), so either side loads the other's model."""

@@ -677,3 +677,39 @@ def sample_normal_rows(out: torch.Tensor, col0: int, loc: torch.Tensor, scale: t
     assert out.dim() == 2
     check(lib.pyz_sample_normal_rows(ptr(out), out.shape[0], out.shape[1], int(col0), loc.numel(), ptr(loc), ptr(scale),
                                      int(seed), _lib.STREAM_PREDICT, int(first_draw) & 0xFFFFFFFF, _stream()))
+
+
+def sample_lowrank_rows(out: torch.Tensor, col0: int, mean: torch.Tensor, diag: torch.Tensor, dev: torch.Tensor,
+                        factor: float, seed: int, first_draw: int):
+    """out[r, col0:col0+len] = mean + diag * z1_r + factor * (z2_r @ dev) for every row r of the (n, stride) CUDA matrix
+    `out`; dev is (k, len), z1_r (len) and z2_r (k) come from draw first_draw + r of the predict stream."""
+    lib = _lib.load()
+    _f32(out, name="out")
+    _f32(mean, name="mean")
+    _f32(diag, (mean.numel(),), "diag")
+    _f32(dev, name="dev")
+    assert out.dim() == 2
+    if dev.dim() != 2 or dev.shape[1] != mean.numel():
+        raise ValueError(f"dev must be (k, {mean.numel()}), not {tuple(dev.shape)}")
+    check(lib.pyz_sample_lowrank_rows(ptr(out), out.shape[0], out.shape[1], int(col0), mean.numel(), ptr(mean), ptr(diag),
+                                      ptr(dev), int(dev.shape[0]), float(factor), int(seed), _lib.STREAM_PREDICT,
+                                      int(first_draw) & 0xFFFFFFFF, _stream()))
+
+
+def gather_rows(out: torch.Tensor, col0: int, bank: torch.Tensor, idx):
+    """out[r, col0:col0+len] = bank[idx[r]] for every row r of the (n, stride) CUDA matrix `out`; bank is a CUDA
+    (n_bank, len) matrix, idx n HOST integers (checked against n_bank here, then uploaded)."""
+    lib = _lib.load()
+    _f32(out, name="out")
+    _f32(bank, name="bank")
+    assert out.dim() == 2
+    if bank.dim() != 2 or bank.shape[0] < 1:
+        raise ValueError("bank must be a (rows >= 1, len) matrix")
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+    if idx.shape[0] != out.shape[0]:
+        raise ValueError(f"{idx.shape[0]} indices for the {out.shape[0]} rows of out")
+    if idx.size and (idx.min() < 0 or idx.max() >= bank.shape[0]):
+        raise IndexError(f"index outside the bank's {bank.shape[0]} rows")
+    idx_d = torch.as_tensor(idx.astype(np.int32)).to(out.device)
+    check(lib.pyz_gather_rows(ptr(out), out.shape[0], out.shape[1], int(col0), bank.shape[1], ptr(bank), bank.shape[0],
+                              ptr(idx_d), _stream()))

@@ -76,10 +76,17 @@ class BayesianModel:
         return W
 
     def sample_weights_device(self, n: int):
-        """The same n joint draws as a CUDA tensor.  Normal / Deterministic posteriors are drawn on the device
-        (Philox: 100 draws of a 159 010-parameter posterior cost 0.2 s of host random numbers otherwise); the
-        other distributions are drawn on the host and uploaded."""
+        """The same n joint draws as a CUDA tensor.  Every result distribution of the package is drawn on the device:
+        Normal and MultivariateNormalDiagPlusLowRank posteriors from the Philox stream of tfd.seed (100 draws of a
+        159 010-parameter posterior cost 0.2 s of host random numbers otherwise), Deterministic ones are copied, Sampled
+        ones are gathered from a device copy of their samples by indices drawn on the host as ``sample_n`` draws them.  A
+        distribution without ``sample_n_device``, or whose ``sample_n_device`` returns False (PYZ_SAMPLE_DEVICE=0, more
+        deviation columns than PYZ_LOWRANK_MAX_K, a sample bank beyond PYZ_SAMPLED_BANK_MAX), is drawn on the host with
+        ``sample_n`` and uploaded.  A model whose ``sample_weights_matrix`` has been replaced (a subclass, an instance
+        attribute) is drawn through the replacement: it defines the draws."""
         import torch
+        if getattr(self.sample_weights_matrix, "__func__", None) is not BayesianModel.sample_weights_matrix:
+            return torch.as_tensor(np.ascontiguousarray(self.sample_weights_matrix(n), dtype=np.float32)).cuda()
         slices = self._interval_slices()
         capable = [getattr(d, "sample_n_device", None) is not None and getattr(d, "_size", 0) <= sl.stop - sl.start
                    for d, sl in zip(self._distributions, slices)]

@@ -455,6 +455,26 @@ int pyz_sample_normal_rows(float *d_out, int64_t n_rows, int64_t row_stride, int
                            const float *d_loc, const float *d_scale, uint64_t seed,
                            uint32_t stream_id, uint32_t first_draw, void *stream);
 
+/* n_rows draws of SWAG's posterior (distributions/MultivariateNormalDiagPlusLowRank.py:32-41) into columns
+ * [col0, col0 + len) of the row-major (n_rows, row_stride) matrix d_out:
+ *   d_out[r][col0 + e] = d_mean[e] + d_diag[e] * z1(r, e) + factor * sum_{c < k} d_dev[c][e] * z2(r, c)
+ * d_mean, d_diag float32[len] (d_diag is the scale of z1, as the reference writes it); d_dev (k, len) row-major, row c =
+ * column c of the reference's deviation matrix; factor = sqrt(1 / (2 (k - 1))) is the caller's.  Draw r uses the Philox
+ * counter (seed, stream_id, first_draw + r): z1(r, e) is its element e, z2(r, c) its element 4 * ceil(len / 4) + c.  The
+ * sum over c is an ascending fmaf chain from 0, then fmaf(factor, sum, fmaf(diag, z1, mean)): the bits of an element do
+ * not depend on n_rows, col0 or how a matrix is cut into calls.  1 <= k <= PYZ_LOWRANK_MAX_K, else PYZ_E_INVALID. */
+#define PYZ_LOWRANK_MAX_K 256
+int pyz_sample_lowrank_rows(float *d_out, int64_t n_rows, int64_t row_stride, int64_t col0, int64_t len,
+                            const float *d_mean, const float *d_diag, const float *d_dev, int k, float factor,
+                            uint64_t seed, uint32_t stream_id, uint32_t first_draw, void *stream);
+
+/* d_out[r][col0 + e] = d_bank[d_idx[r]][e]: n_rows rows of the row-major (n_bank, len) matrix d_bank, picked by the
+ * DEVICE indices d_idx (int32[n_rows]), into columns [col0, col0 + len) of the row-major (n_rows, row_stride) matrix
+ * d_out -- the draws of distributions/Sampled.py:29-32 from samples that stay on the device.  The caller checks the
+ * indices it uploads; a row whose index is outside [0, n_bank) is not written (and nothing is read for it). */
+int pyz_gather_rows(float *d_out, int64_t n_rows, int64_t row_stride, int64_t col0, int64_t len,
+                    const float *d_bank, int64_t n_bank, const int32_t *d_idx, void *stream);
+
 /* ---- device memory for callers that have no allocator of their own (a TensorFlow / NumPy host process binding
  * this library from the reference's step(), INTEGRATION.md route B; torch-ROCm callers pass their tensors'
  * storage instead).  pyz_upload / pyz_download copy between a HOST buffer and device memory and return when
