@@ -2,6 +2,7 @@
 // Host-side orchestration only: shape checks, workspace, kernel launches.
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 
@@ -411,8 +412,10 @@ int wgrad_layers(pyz_mlp *m, int P, const float *x, const int32_t *row_idx, cons
     ly.delta_pstride = (long long)m->max_batch * ly.N;
     ly.w_off = m->w_off[l];
     ly.tile0 = tiles;
+    a.tile0[l] = tiles;
     tiles += ((ly.K + 1 + 31) / 32) * ((ly.N + 31) / 32);
   }
+  for (int l = m->L; l < PYZ_MAX_LAYERS; ++l) a.tile0[l] = INT_MAX;   // no tile id reaches it
   a.row_idx = row_idx;
   a.ctl = ctl;
   a.part = m->part;

@@ -72,6 +72,44 @@ __device__ unsigned long long pyz_dbg_buf[PYZ_STAMP_KERNELS][PYZ_STAMP_BLOCKS][P
 // instead of exec-masked vector compares
 __device__ __forceinline__ int pyz_wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
+// Kernel arguments arrive through scalar loads that the compiler places where a value is first used: behind every early
+// branch it starts another group, each with a wait of its own (five or six dependent round trips in front of the first
+// operand load of the step kernels).  An empty `asm volatile("; arguments in one trip" ::"s"(a), "s"(b), ...)` makes the
+// listed (wave-uniform, 32- or 64-bit) values exist at that point of the program: their loads are requested together
+// there and answered by one wait.
+
+// The step scalars a kernel behind the first one needs, fetched with the loads next to each other and one wait (not one
+// load per field where each is first used, the row offset behind a branch).  The block was written by another kernel:
+// ordinary vector loads, made scalar again with readfirstlane.
+struct PyzCtlHot {
+  int batch;
+  float lr;
+  long long n, row_off;
+};
+// two halves, so that a kernel can put other requests (its layer's arguments) between the request and the wait
+__device__ __forceinline__ PyzCtlHot pyz_ctl_request(const StepCtl *ctl) {
+  PyzCtlHot c;
+  c.batch = ctl->batch;
+  c.lr = ctl->lr;
+  c.n = ctl->n;
+  c.row_off = ctl->row_off;
+  return c;
+}
+__device__ __forceinline__ PyzCtlHot pyz_ctl_arrived(const PyzCtlHot &raw) {
+  int b = raw.batch;
+  float lr = raw.lr;
+  long long n = raw.n, ro = raw.row_off;
+  asm volatile("; step scalars" : "+v"(b), "+v"(lr), "+v"(n), "+v"(ro));   // all four have arrived here, whichever path uses them
+  PyzCtlHot c;
+  c.batch = __builtin_amdgcn_readfirstlane(b);
+  c.lr = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lr)));
+  const unsigned nl = __builtin_amdgcn_readfirstlane((int)(unsigned)n), nh = __builtin_amdgcn_readfirstlane((int)(n >> 32));
+  const unsigned rl = __builtin_amdgcn_readfirstlane((int)(unsigned)ro), rh = __builtin_amdgcn_readfirstlane((int)(ro >> 32));
+  c.n = (long long)(((unsigned long long)nh << 32) | nl);
+  c.row_off = (long long)(((unsigned long long)rh << 32) | rl);
+  return c;
+}
+
 // Eager step entry points do not spend a launch on the step scalars: the FIRST kernel of the step gets
 // them by value (`init`), uses them, and its first thread publishes them in the device StepCtl for the
 // kernels behind it (which start after that kernel has ended).

@@ -22,30 +22,36 @@
 //   2. loss row terms, delta_L  (SparseCategoricalCrossentropy / MeanSquaredError as
 //                                in k_loss_scce / k_loss_mse: Dataset.py:152-159)
 //   3. delta_{L-1} = (delta_L W^T) * act'(h_in)   (MFMA with delta_L from LDS)
+// (Field order: what k_head_rows reads in front of its first operand load fills the first two 64-byte lines and is asked
+// for in one trip, see DenseArgs.)
 struct HeadArgs {
+  // ---- line 0
   const float *hin;          // (P, max_batch, K) input of the last layer, or the data x when L == 1
   long long hin_pstride;
-  int lda;
-  const int32_t *row_idx;    // gather of hin rows (only when hin is the data, L == 1) and of the labels
-  int gather_hin;
   const float *theta;
   long long theta_pstride;
   long long w_off;
-  int K, N;
-  int loss, act_last, act_prev, vec;
+  const StepCtl *ctl;
+  const int32_t *row_idx;    // gather of hin rows (only when hin is the data, L == 1) and of the labels
+  const StepCtl *gate;       // when set: nothing happens on steps with gate->n % gate_mod == 0 (see DenseArgs)
+  // ---- line 1
   const void *y;
+  double *part;              // (P, nblk) per-workgroup sums of the row losses
+  int lda;
+  int K, N;
+  int loss;
+  int gather_hin;
+  int gate_mod;
+  int init_on;
+  int nblk;
+  int act_last, act_prev, vec;
+  int wt;                    // write-through stores for the outputs (pyz_st)
+  // ---- the rest
   float *out_last;           // optional (P, max_batch, N): logits (softmax layer) / outputs
   float *delta_last;         // (P, max_batch, N) or nullptr (loss only)
   float *delta_prev;         // (P, max_batch, K) or nullptr
   long long last_pstride, prev_pstride;
-  double *part;              // (P, nblk) per-workgroup sums of the row losses
-  int nblk;
-  const StepCtl *ctl;
   StepCtl init;              // the step scalars by value when the head is the first kernel of an eager step (L == 1)
-  int init_on;
-  int wt;                    // write-through stores for the outputs (pyz_st)
-  const StepCtl *gate;       // when set: nothing happens on steps with gate->n % gate_mod == 0 (see DenseArgs)
-  int gate_mod;
   // k_head_rows behind a split-reduction forward (k_dense_fwd_ring, k_split): the hidden layer arrives as n_hparts <= 8 raw
   // partial sums (hparts + s * hpart_stride + row * K + unit); the head adds them in split order, then the hidden layer's
   // bias (bias_prev[unit]) and activation (act_prev), and stores the row of activations to h_store for the weight gradients
@@ -321,6 +327,15 @@ __device__ __forceinline__ void pyz_head_load_w(const HeadArgs &g, const int p, 
   W.bias_mine = pyz_buf_load(rw, l < N ? 4u * ((unsigned)K * (unsigned)N + (unsigned)l) : OOB, 0u);  // lane c: b[c]
 }
 
+// the lane's units of input row `hrow` (units past K read as zero)
+template <int UT>
+__device__ __forceinline__ void pyz_head_load_h(const HeadArgs &g, const int p, const long long hrow, const int l, float (&hv)[UT]) {
+  const float *hp = g.hin + p * g.hin_pstride + hrow * g.lda;
+  const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(hp), 0, g.K * 4, 0x00020000);
+#pragma unroll
+  for (int t = 0; t < UT; ++t) hv[t] = pyz_buf_load(rh, 4u * (unsigned)(l + 64 * t), 0u);
+}
+
 // The head of ONE batch row m by ONE wave (lane l).  PRELOADED: W already holds the wave's share of [W; b] (several
 // rows per wave); else it is fetched here, behind the row's own loads (one row per wave: the order of round 1 --
 // with the 48 strided [W; b] loads in front of them the row's input and label chain start 0.4 us later).
@@ -331,13 +346,11 @@ template <int UT, int NP, bool PRELOADED, bool HP = false>
 __device__ __forceinline__ void pyz_head_row(const HeadArgs &g, const int batch, const long long row_off, const int p,
                                              const int m, const int l, PyzHeadW<UT, NP> &W) {
   const int K = g.K, N = g.N;
-  long long yrow = m;
-  if (g.row_idx) yrow = g.row_idx[row_off + m];
-  const float *hp = g.hin + p * g.hin_pstride + (g.gather_hin ? yrow : (long long)m) * g.lda;
-  // units past K read as zero.  The class loops below are straight-line code over the NP padded
+  int yidx = m;   // the row's index in the data set: requested here, waited for where the label is loaded (below)
+  if (g.row_idx) yidx = g.row_idx[row_off + m];
+  // The class loops below are straight-line code over the NP padded
   // classes: no per-class branches (conditional writes into the register arrays would turn them
   // into whole-vector copies).
-  const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(hp), 0, K * 4, 0x00020000);
   float hv[UT], z[NP];
   if constexpr (HP) {
     // the hidden layer as raw partial sums of a split reduction: eight loads per unit in flight together (splits past
@@ -366,12 +379,25 @@ __device__ __forceinline__ void pyz_head_row(const HeadArgs &g, const int batch,
       if (u < K) pyz_st(g.h_store + (long long)m * K + u, hv[t], g.wt);
     }
   } else {
-#pragma unroll
-    for (int t = 0; t < UT; ++t) hv[t] = pyz_buf_load(rh, 4u * (unsigned)(l + 64 * t), 0u);
+    // A branch, not `gather_hin ? index : m`: behind the select the row's loads (and the 48 loads of [W; b] behind them)
+    // waited for the row index, which only a gathered input (L == 1) and the label need.
+    if (g.gather_hin) {
+      asm volatile("; gathered input: the row index is needed here" ::: "memory");   // (keeps this a branch)
+      // (made scalar HERE: left to the compiler, the two arms become one load behind a select of the row, and the scalar
+      //  copy of the index -- with its wait -- moves back to where the index was loaded)
+      pyz_head_load_h<UT>(g, p, __builtin_amdgcn_readfirstlane(yidx), l, hv);
+    } else {
+      pyz_head_load_h<UT>(g, p, m, l, hv);
+    }
   }
   if (!PRELOADED) pyz_head_load_w<UT, NP>(g, p, l, W);
   const auto &wv = W.wv;
   const float bias_mine = W.bias_mine;
+  // The index is wave-uniform, and as a scalar it is waited for where it was loaded (readfirstlane), in front of every
+  // operand load above, whatever the branch says.  From here on it is a per-lane value: the label is loaded through a
+  // vector address and the wait for the index stands here, behind the row's and [W; b]'s loads.
+  asm volatile("; the row index arrives here" : "+v"(yidx));
+  const long long yrow = yidx;
   int ylab = 0;
   if (g.loss == PYZ_LOSS_SCCE) ylab = reinterpret_cast<const int32_t *>(g.y)[yrow];
   PYZ_STAMP(1, 1);
@@ -497,8 +523,26 @@ template <int UT, int NP, int RW = 1, bool HP = false>
 __global__ void __launch_bounds__(256) k_head_rows(HeadArgs g) {
   PYZ_STAMP(1, 0);
   const int w = pyz_wave_id(), l = threadIdx.x & 63;
+  // the first two lines of the arguments in one trip, the gate test out of the same answer (see k_dense_fwd)
+  asm volatile("; arguments in one trip" ::"s"(g.hin), "s"(g.hin_pstride), "s"(g.theta), "s"(g.theta_pstride), "s"(g.w_off),
+               "s"(g.ctl), "s"(g.row_idx), "s"(g.gate), "s"(g.y), "s"(g.part), "s"(g.lda), "s"(g.K), "s"(g.N), "s"(g.loss),
+               "s"(g.gather_hin), "s"(g.gate_mod), "s"(g.init_on), "s"(g.nblk), "s"(g.act_last), "s"(g.act_prev), "s"(g.vec),
+               "s"(g.wt));
   if (g.gate && g.gate->n % g.gate_mod == 0) return;
-  const StepCtl ctl = pyz_ctl_first(g.ctl, g.init, g.init_on);
+  // The step scalars: a branch, not pyz_ctl_first's select -- the select asks for the 40 bytes of g.init (another trip to
+  // the argument segment, in front of the operand loads) in every launch, the branch only where the head is the first
+  // kernel of an eager step.
+  StepCtl ctl;
+  if (g.init_on) {
+    asm volatile("; the step scalars by value" ::: "memory");   // (keeps this a branch)
+    ctl = pyz_ctl_first(g.ctl, g.init, 1);
+  } else {
+    // both scalars with one wait, here: a row offset still in flight at the batch test stays "pending" on the path
+    // without a row table, and the register it would land in is then waited for in the middle of the operand loads
+    const PyzCtlHot c = pyz_ctl_arrived(pyz_ctl_request(g.ctl));
+    ctl.batch = c.batch;
+    ctl.row_off = c.row_off;
+  }
   const int batch = ctl.batch, p = blockIdx.y;
   const int m0 = (blockIdx.x * 4 + w) * RW;  // this wave's first batch row (scalar)
   if (m0 >= batch) {
@@ -671,18 +715,33 @@ struct WgradLayer {
 #define PYZ_UPD_BBB 3   // BBB.py:152-201 (theta = mu, mean = rho, sq_mean = the sampled w; read only)
 #define PYZ_UPD_SWAG 4  // SWAG.py:61-92 (SGD update; gated moments; one deviation row)
 
+// (Field order: what a tile workgroup of k_wgrad_all reads in front of its first operand load comes first -- 136 bytes,
+// asked for in one trip -- and the layer it then picks is ONE 64-byte entry of lay[], which starts on a multiple of 64
+// (the duties' fields fill the gap); see DenseArgs.  With the layers in front, those fields lay 1 KB into the segment and
+// were fetched where each was first used.)
 struct WgradArgs {
-  WgradLayer lay[PYZ_MAX_LAYERS];
-  int L;
   int tiles;                  // tiles of all layers; the launch has one more workgroup, for the step duties
-  const int32_t *row_idx;
-  const StepCtl *ctl;
+  int L;
   int mode;
+  int wt;                     // write-through stores for the updated state (pyz_st)
+  const StepCtl *ctl;
+  const int32_t *row_idx;
+  float *theta, *mean, *sq_mean;
+  const float *unit_noise;    // SGLD: injected N(0,1); BBB: injected eps
+  uint64_t seed;
+  int tile0[PYZ_MAX_LAYERS];  // lay[l].tile0 again (INT_MAX past L): a tile finds its layer by comparing with all of them at once
+  // duties of workgroup 0 at the end of the step: loss and the next step's scalars
+  const double *part;
+  int nblk;
+  int loss_indexed;
+  float *loss;
+  StepCtl *next;
+  const int32_t *tab_bs;
+  const float *tab_lr;
+  int *nonfinite;             // device counter of steps with a NaN / Inf loss (may be nullptr)
+  WgradLayer lay[PYZ_MAX_LAYERS];
   float *grad;                // mode NONE: (P, D)
   long long grad_pstride;
-  float *theta, *mean, *sq_mean;
-  uint64_t seed;
-  const float *unit_noise;    // SGLD: injected N(0,1); BBB: injected eps
   // SWAG only: dev_row = the (D) row of the deviation matrix that receives theta - mean, or nullptr
   float *dev_row;
   int swag_update;            // moments / deviation updated at this step (n % frequency == 0)
@@ -704,20 +763,12 @@ struct WgradArgs {
   // part_kl_next[workgroup]; nullptr = the step's own k_bbb_sample launch does both
   float *w_next;
   double *part_kl_next;
-  // duties of workgroup 0 at the end of the step: loss and the next step's scalars
-  const double *part;
-  int nblk;
-  float *loss;
-  int loss_indexed;
-  StepCtl *next;
-  const int32_t *tab_bs;
-  const float *tab_lr;
-  long long row_stride;
-  int *nonfinite;             // device counter of steps with a NaN / Inf loss (may be nullptr)
+  long long row_stride;       // (duties: the row-table stride between two steps)
   float *ploss;               // particle-batched gradient passes: loss[p] = (sum of particle p's row partials) / batch
-  int wt;                     // write-through stores for the updated state (pyz_st)
-  PrepArgs prep;              // chained runs: the workgroups past the duties workgroup assemble the NEXT step's batch
+  PrepArgs prep;             // chained runs: the workgroups past the duties workgroup assemble the NEXT step's batch
 };
+
+static_assert(offsetof(WgradArgs, lay) % 64 == 0 && sizeof(WgradLayer) == 64, "a layer's entry is one 64-byte line");
 
 // ---------------------------------------------------------------- the optimizer updates (shared by the
 // epilogue of k_wgrad_all; kept apart from the tile code so that every mode is one readable block)
@@ -735,16 +786,22 @@ __device__ __forceinline__ PyzUpdOut pyz_update_math(const WgradArgs &g, const i
   o.th = o.mu = o.sq = o.dev = 0.0f;
   o.wr_mu = o.wr_sq = o.wr_dev = false;
   o.dev_row = nullptr;
+  // The roundings of the SGD / SWAG / SGLD arms are written out (fmaf = one rounding; everything else in these arms rounds
+  // per operation: contraction is off).  They are what k_wgrad_all<16> compiled to while these arms stood in one body with
+  // a run-time mode -- there the products mu0 * fn and sq0 * fn were shared by the SWAG and the SGLD arm in front of the
+  // branch, out of reach of the sums that might have absorbed them.  Left to the compiler, which of the sums becomes an
+  // fma changes with the instantiation and with the code around the call ("The serial head and tail").
   if (mode == PYZ_UPD_SGD) {
-    o.th = th0 - lr * gv;
+    o.th = __builtin_fmaf(-lr, gv, th0);
   } else if (mode == PYZ_UPD_SWAG) {
-    const float th = th0 - lr * gv;
+#pragma clang fp contract(off)
+    const float th = __builtin_fmaf(-lr, gv, th0);
     o.th = th;
     const bool upd = g.swag_freq > 0 ? (nstep % g.swag_freq == 0) : (g.swag_update != 0);
     if (upd) {
       const float fn = (float)nstep, fn1 = fn + 1.0f;
       o.mu = (mu0 * fn + th) / fn1;
-      o.sq = (sq0 * fn + th * th) / fn1;
+      o.sq = __builtin_fmaf(th, th, sq0 * fn) / fn1;
       o.dev = th - o.mu;
       o.wr_mu = o.wr_sq = true;
       // columns are appended until there are k; afterwards the LAST one is replaced (SWAG.py:85-89, as written)
@@ -754,6 +811,9 @@ __device__ __forceinline__ PyzUpdOut pyz_update_math(const WgradArgs &g, const i
       o.wr_dev = o.dev_row != nullptr;
     }
   } else if (mode == PYZ_UPD_BBB) {
+    // (Deliberately NOT written out like the arms above: which of this arm's thirty-odd operations fuse is the compiler's
+    //  choice, it differed between the instantiations before, and it moves in the last bits when the code around the call
+    //  changes -- DESIGN 5, "The serial head and tail".  Pin it here when that matters.)
     // th0 = mu, mu0 = rho, sq0 = the sampled w, zz = eps, gv = d loss / d w   (k_bbb_update's arithmetic)
     const float pmean = g.pm_vec ? g.pm_vec[e] : g.prior_mean;
     const float sp = pyz_softplus(g.pr_vec ? g.pr_vec[e] : g.prior_rho), isp2 = 1.0f / (sp * sp);
@@ -768,12 +828,13 @@ __device__ __forceinline__ PyzUpdOut pyz_update_math(const WgradArgs &g, const i
     o.mu = rho - blr * (zz * sig * g_w + g_rho);
     o.wr_mu = true;
   } else if (mode == PYZ_UPD_SGLD) {
+#pragma clang fp contract(off)
     const float fn = (float)nstep, fn1 = fn + 1.0f;
-    const float noise = lr * zz;
-    const float th = th0 + (-lr) * (gv + noise);
+    const float gn = __builtin_fmaf(lr, zz, gv);      // the gradient plus the noise lr * zz
+    const float th = __builtin_fmaf(-lr, gn, th0);
     o.th = th;
     o.mu = (mu0 * fn + th) / fn1;
-    o.sq = (sq0 * fn + th * th) / fn1;
+    o.sq = __builtin_fmaf(th, th, sq0 * fn) / fn1;
     o.wr_mu = o.wr_sq = true;
   }
   return o;
@@ -853,51 +914,38 @@ __device__ __forceinline__ void pyz_wgrad_accumulate(f32x16 &acc, const float *a
   }
 }
 
-// S = waves per workgroup (compile time: the epilogue prefetches 16/S elements per thread).
-// PLAIN: the launch only writes gradients (g.mode == PYZ_UPD_NONE: particle-batched passes of SVGD / HMC, loss_grad):
-// no optimizer state is fetched, so the four prefetch arrays of the epilogue do not exist -- for S = 1 that is 64
-// registers per lane, i.e. the difference between two and four resident waves per SIMD.
-template <int S, bool PLAIN = false>
-__global__ void __launch_bounds__(64 * S) k_wgrad_all(WgradArgs g) {
-  extern __shared__ float red[];
-  PYZ_STAMP(2, 0);
+// One tile of k_wgrad_all, MODE (the optimizer update) a compile-time constant: the kernel branches once on g.mode, so the
+// prefetch hook and the epilogue of an SGLD step hold no other mode's instructions, registers or branches (as one body
+// with a run-time mode, BBB's fused sampling -- softplus, logs, the log q - log p reduction -- and SWAG's gated moments lay
+// between the SGLD instructions).
+template <int S, bool PLAIN, int MODE>
+__device__ __forceinline__ void pyz_wgrad_tile(const WgradArgs &g, float *red) {
   constexpr int EPT = 16 / S;  // tile elements per thread in the epilogue
   const int w = pyz_wave_id(), l = threadIdx.x & 63;
   const int r = l & 31, h = l >> 5;
-  // workgroup `tiles` (the last id) owns no tile: its first wave does the duties of the step that do
-  // not depend on the gradient, off the critical path of the tile workgroups
-  if (blockIdx.x >= (unsigned)g.tiles) {  // (without a batch to prepare, ids past `tiles` + 1 only pad the launch)
-    if (blockIdx.x == (unsigned)g.tiles && blockIdx.y == 0 && w == 0) pyz_step_duties(g, l);
-    if (blockIdx.x == (unsigned)g.tiles && w == 0 && g.ploss) {   // every particle's spare workgroup: its loss (k_loss_finalize)
-      const double tot = pyz_sum_partials(g.part + (long long)blockIdx.y * g.nblk, g.nblk);
-      if (l == 0) {
-        g.ploss[blockIdx.y] = (float)(tot / (double)g.ctl->batch);
-        pyz_note_loss(g.nonfinite, g.ploss[blockIdx.y]);
-      }
-    }
-    if (!PLAIN && blockIdx.x > (unsigned)g.tiles && blockIdx.y == 0 && g.prep.src) {
-      const int i2 = g.ctl->i + 1;
-      if (i2 < g.ctl->n_run)
-        pyz_prep_rows(g.prep, g.prep.row_idx + g.ctl->row_off + g.prep.row_stride, g.prep.tab_bs[i2],
-                      (int)blockIdx.x - g.tiles - 1, (int)gridDim.x - g.tiles - 1, (int)blockIdx.x);
-      PYZ_STAMP(2, 3);
-    }
-    return;
-  }
   const int tile = pyz_xcd_remap(blockIdx.x, g.tiles);
+  // the tile's layer: tile0[] is ascending (INT_MAX past the last layer), all sixteen arrived with the first arguments --
+  // a count of compares, not a walk with one dependent load per layer
   int li = 0;
-  while (li + 1 < g.L && tile >= g.lay[li + 1].tile0) ++li;
+#pragma unroll
+  for (int j = 1; j < PYZ_MAX_LAYERS; ++j) li += tile >= g.tile0[j] ? 1 : 0;
+  li = __builtin_amdgcn_readfirstlane(li);   // (an index, then one address: else the sum is carried out on sixteen address candidates)
   const WgradLayer &ly = g.lay[li];
-  const int batch = g.ctl->batch;
+  // the step scalars (written by another kernel: vector loads) and the layer's entry travel together: one wait each
+  const PyzCtlHot ctl_raw = pyz_ctl_request(g.ctl);
+  asm volatile("; the layer in one trip" ::"s"(ly.in), "s"(ly.in_pstride), "s"(ly.delta), "s"(ly.delta_pstride), "s"(ly.w_off),
+               "s"(ly.lda), "s"(ly.K), "s"(ly.N), "s"(ly.tile0), "s"(ly.gather));
+  const PyzCtlHot ctl = pyz_ctl_arrived(ctl_raw);
+  const int batch = ctl.batch;
   const int K = ly.K, N = ly.N;
   const int tiles_n = (N + 31) >> 5;
   const int t = tile - ly.tile0;
   const int i0 = (t / tiles_n) * 32, n0 = (t % tiles_n) * 32;
   const int p = blockIdx.y;
   const long long w_off = ly.w_off;
-  const int mode = PLAIN ? PYZ_UPD_NONE : g.mode;
-  const long long nstep = g.ctl->n;
-  const float lr = g.ctl->lr;
+  constexpr int mode = PLAIN ? PYZ_UPD_NONE : MODE;
+  const long long nstep = ctl.n;
+  const float lr = ctl.lr;
 
   // -- epilogue operands of this thread's elements and the Philox noise: needed only after the
   //    reduction, so they are fetched / generated right behind the first group of operand loads
@@ -950,7 +998,7 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_all(WgradArgs g) {
   const bool is_w = i < K, is_b = i == K;
   const float *ap = ly.in + p * ly.in_pstride + ic;
   const float *dp = ly.delta + p * ly.delta_pstride + n;
-  const int32_t *idx = (ly.gather && g.row_idx) ? g.row_idx + g.ctl->row_off : nullptr;
+  const int32_t *idx = (ly.gather && g.row_idx) ? g.row_idx + ctl.row_off : nullptr;
   f32x16 acc = {0};
   const int steps = (batch + 1) >> 1;
   int s = (steps * w) / S;
@@ -1049,6 +1097,54 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_all(WgradArgs g) {
     if (threadIdx.x == 0) g.part_kl_next[blockIdx.x] = tot;
   }
   PYZ_STAMP(2, 3);
+}
+
+// S = waves per workgroup (compile time: the epilogue prefetches 16/S elements per thread).
+// PLAIN: the launch only writes gradients (g.mode == PYZ_UPD_NONE: particle-batched passes of SVGD / HMC, loss_grad):
+// no optimizer state is fetched, so the four prefetch arrays of the epilogue do not exist -- for S = 1 that is 64
+// registers per lane, i.e. the difference between two and four resident waves per SIMD.
+template <int S, bool PLAIN = false>
+__global__ void __launch_bounds__(64 * S) k_wgrad_all(WgradArgs g) {
+  extern __shared__ float red[];
+  PYZ_STAMP(2, 0);
+  const int w = pyz_wave_id(), l = threadIdx.x & 63;
+  // what a tile workgroup needs in front of its first operand load, in one trip (see WgradArgs)
+  asm volatile("; arguments in one trip" ::"s"(g.tiles), "s"(g.mode), "s"(g.ctl), "s"(g.row_idx), "s"(g.tile0[1]),
+               "s"(g.tile0[2]), "s"(g.tile0[3]), "s"(g.tile0[4]), "s"(g.tile0[5]), "s"(g.tile0[6]), "s"(g.tile0[7]),
+               "s"(g.tile0[8]), "s"(g.tile0[9]), "s"(g.tile0[10]), "s"(g.tile0[11]), "s"(g.tile0[12]), "s"(g.tile0[13]),
+               "s"(g.tile0[14]), "s"(g.tile0[15]));
+  // workgroup `tiles` (the last id) owns no tile: its first wave does the duties of the step that do
+  // not depend on the gradient, off the critical path of the tile workgroups
+  if (blockIdx.x >= (unsigned)g.tiles) {  // (without a batch to prepare, ids past `tiles` + 1 only pad the launch)
+    if (blockIdx.x == (unsigned)g.tiles && blockIdx.y == 0 && w == 0) pyz_step_duties(g, l);
+    if (blockIdx.x == (unsigned)g.tiles && w == 0 && g.ploss) {   // every particle's spare workgroup: its loss (k_loss_finalize)
+      const double tot = pyz_sum_partials(g.part + (long long)blockIdx.y * g.nblk, g.nblk);
+      if (l == 0) {
+        g.ploss[blockIdx.y] = (float)(tot / (double)g.ctl->batch);
+        pyz_note_loss(g.nonfinite, g.ploss[blockIdx.y]);
+      }
+    }
+    if (!PLAIN && blockIdx.x > (unsigned)g.tiles && blockIdx.y == 0 && g.prep.src) {
+      const int i2 = g.ctl->i + 1;
+      if (i2 < g.ctl->n_run)
+        pyz_prep_rows(g.prep, g.prep.row_idx + g.ctl->row_off + g.prep.row_stride, g.prep.tab_bs[i2],
+                      (int)blockIdx.x - g.tiles - 1, (int)gridDim.x - g.tiles - 1, (int)blockIdx.x);
+      PYZ_STAMP(2, 3);
+    }
+    return;
+  }
+  // (uniform) one instruction stream per update mode
+  if constexpr (PLAIN) {
+    pyz_wgrad_tile<S, true, PYZ_UPD_NONE>(g, red);
+  } else {
+    switch (g.mode) {
+      case PYZ_UPD_SGLD: pyz_wgrad_tile<S, false, PYZ_UPD_SGLD>(g, red); break;
+      case PYZ_UPD_SGD: pyz_wgrad_tile<S, false, PYZ_UPD_SGD>(g, red); break;
+      case PYZ_UPD_SWAG: pyz_wgrad_tile<S, false, PYZ_UPD_SWAG>(g, red); break;
+      case PYZ_UPD_BBB: pyz_wgrad_tile<S, false, PYZ_UPD_BBB>(g, red); break;
+      default: pyz_wgrad_tile<S, false, PYZ_UPD_NONE>(g, red); break;
+    }
+  }
 }
 
 // pyz_wgrad_accumulate with a second chain: acc2 += (a^2) (fb d)^2 from the masked operands of every step (k_wgrad_adam)

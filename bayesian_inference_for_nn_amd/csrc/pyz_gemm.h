@@ -28,34 +28,42 @@
 
 #include "pyz_common.h"
 
+// Field order: a wave reads its arguments with scalar loads, a 64-byte line per request at best, and the compiler asks
+// for each group where it is first used -- one round trip per group, all of them in front of the first operand load.
+// What k_dense_fwd needs before that load therefore sits together in the first two lines (the kernel asks for them in
+// one go, see pyz_common.h); everything only some launches use comes behind.
 struct DenseArgs {
+  // ---- line 0
   const float *in;            // A-side activations (forward/weight-grad: layer input; data-grad: delta)
   long long in_pstride;       // particle stride of `in` (0 when shared, e.g. the data batch)
-  int lda;                    // row stride of `in`
   const float *theta;         // (P, D) flat parameters
   long long theta_pstride;
   long long w_off;            // offset of this layer's kernel in the flat vector
+  int lda;                    // row stride of `in`
   int K, N;                   // layer input / output width
+  int vec;                    // float4 loads legal along the reduction axis
+  int rows_cap;               // forward, k_dense_fwd: > 0 = readable rows of a contiguous `in` (see the kernel)
+  int gate_mod;               // (see gate)
+  // ---- line 1
   float *out;                 // destination (see each kernel)
   long long out_pstride;
-  const float *aux;           // data-grad: previous layer's output (for act'); weight-grad: delta
-  long long aux_pstride;
-  int act;                    // forward: this layer's activation; data-grad: previous layer's
-  int vec;                    // float4 loads legal along the reduction axis
   const StepCtl *ctl;         // batch (rows) and row-index offset of this step
   const int32_t *row_idx;     // optional gather of `in` rows (layer 0 only)
   float *gather_out;          // optional (max_batch, K): contiguous copy of the gathered rows (forward, layer 0)
-  StepCtl init;               // forward only: the step scalars by value when this is the first kernel of an eager step
-  int init_on;
+  const StepCtl *gate;        // forward (k_dense_fwd): when set, the launch does nothing on steps with gate->n % gate_mod == 0
+                              // (the validation forward of a device-resident BBB run: BBB.py:203 skips every tenth step)
+  int act;                    // forward: this layer's activation; data-grad: previous layer's
   int wt;                     // forward: write-through stores for the activations (pyz_st)
-  int rows_cap;               // forward, k_dense_fwd: > 0 = readable rows of a contiguous `in` (see the kernel)
+  int init_on;
+  // ---- the rest
+  const float *aux;           // data-grad: previous layer's output (for act'); weight-grad: delta
+  long long aux_pstride;
+  StepCtl init;               // forward only: the step scalars by value when this is the first kernel of an eager step
   int n_part, grid_rows;      // forward, k_dense_fwd_ring (1-D grid): particles and rows of the launch
   int n_cgrp, cgrp_w;         // forward, k_dense_fwd_ring: column groups per row block (layers wider than one workgroup's 200 columns) and their width
   int k_split;                // forward, k_dense_fwd_ring: > 1 = the reduction cut into k_split ranges of slabs, one workgroup each; raw partial sums
   float *part_out;            //   (no bias, no activation) go to part_out + split * part_stride + row * N + column: the consumer
   long long part_stride;      //   (k_head_rows) adds them in split order, then the bias and the activation
-  const StepCtl *gate;        // forward (k_dense_fwd): when set, the launch does nothing on steps with gate->n % gate_mod == 0
-  int gate_mod;               // (the validation forward of a device-resident BBB run: BBB.py:203 skips every tenth step)
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2), so ids
@@ -124,6 +132,28 @@ __device__ __forceinline__ float pyz_bce_row(float z, float y, float &p) {
 // and hand each element to `store(row_in_tile, col_in_tile, value)`.
 // C/D layout of v_mfma_f32_32x32x2_f32: col = lane & 31,
 // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
+// The combine of S waves' partials with S known at compile time: a thread owns 16 / S elements and issues the S reads
+// of every one of them (16 LDS reads) before the first add, so the combine costs one LDS round trip.  Each element is
+// summed as before: wave 0's partial first, then waves 1 .. S - 1 one after the other (the same bits).  With S a
+// run-time value the adds of the later waves were a loop of read, wait, add: up to eight dependent round trips.
+template <int S, class F>
+__device__ __forceinline__ void pyz_tile_combine(const float *red, F &store) {
+  constexpr int EPT = 16 / S;
+  float v[EPT][S];
+#pragma unroll
+  for (int q = 0; q < EPT; ++q)
+#pragma unroll
+    for (int ww = 0; ww < S; ++ww) v[q][ww] = red[ww * 1024 + (int)threadIdx.x + q * 64 * S];
+#pragma unroll
+  for (int q = 0; q < EPT; ++q) {
+    const int e = (int)threadIdx.x + q * 64 * S;
+    float s = v[q][0];
+#pragma unroll
+    for (int ww = 1; ww < S; ++ww) s += v[q][ww];
+    store(e >> 5, e & 31, s);
+  }
+}
+
 template <class F>
 __device__ __forceinline__ void pyz_tile_epilogue(const f32x16 &acc, float *red, F store) {
   const int S = blockDim.x >> 6, w = pyz_wave_id(), l = threadIdx.x & 63;
@@ -137,10 +167,12 @@ __device__ __forceinline__ void pyz_tile_epilogue(const f32x16 &acc, float *red,
 #pragma unroll
   for (int i = 0; i < 16; ++i) my[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = acc[i];
   __syncthreads();
-  for (int e = threadIdx.x; e < 1024; e += blockDim.x) {
-    float s = red[e];
-    for (int ww = 1; ww < S; ++ww) s += red[ww * 1024 + e];
-    store(e >> 5, e & 31, s);
+  switch (S) {   // (uniform) the launches pick S in {1, 2, 4, 8, 16}: pyz_pick_waves
+    case 2: pyz_tile_combine<2>(red, store); break;
+    case 4: pyz_tile_combine<4>(red, store); break;
+    case 8: pyz_tile_combine<8>(red, store); break;
+    case 16: pyz_tile_combine<16>(red, store); break;
+    default: __builtin_trap();   // no launch has another wave count; a silent pass would read LDS it was not given
   }
 }
 
@@ -335,6 +367,12 @@ __global__ void k_dense_fwd(DenseArgs g) {
   const int S = blockDim.x >> 6, w = pyz_wave_id(), l = threadIdx.x & 63;
   const int r = l & 31, h = l >> 5;
   const int tiles_n = (g.N + 31) >> 5;
+  // the first two lines of the arguments in one trip; the gate test (only the validation forward of a BBB run has one)
+  // comes out of the same answer instead of a round trip of its own in front of everything else
+  asm volatile("; arguments in one trip" ::"s"(g.in), "s"(g.in_pstride), "s"(g.theta), "s"(g.theta_pstride), "s"(g.w_off),
+               "s"(g.lda), "s"(g.K), "s"(g.N), "s"(g.vec), "s"(g.rows_cap), "s"(g.gate_mod), "s"(g.out), "s"(g.out_pstride),
+               "s"(g.ctl), "s"(g.row_idx), "s"(g.gather_out), "s"(g.gate), "s"(g.act), "s"(g.wt), "s"((int)gridDim.x),
+               "s"((int)blockDim.x));   // (the launch dimensions are arguments too, behind the struct)
   if (g.gate && g.gate->n % g.gate_mod == 0) return;   // (uniform)
   const int tile = pyz_xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (tile / tiles_n) * 32, n0 = (tile % tiles_n) * 32;
