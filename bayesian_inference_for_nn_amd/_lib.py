@@ -13,7 +13,7 @@ LOSS = {"scce": 0, "mse": 1, "bce": 2}
 SWEEP = {"gauss_seidel": 0, "jacobi": 1}
 GAMMA_MEDIAN = -1.0       # PYZ_SVGD_GAMMA_MEDIAN
 
-STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM, STREAM_BSAM = 0, 1, 2, 3, 4, 5, 6
+STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM, STREAM_BSAM, STREAM_CORRUPT = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class PyzError(RuntimeError):
@@ -79,6 +79,8 @@ SIGNATURES = {
     "pyz_predict": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
     "pyz_predict_moments": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
     "pyz_input_grad": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, _f, _p, _f, _p, _p, _p]),
+    "pyz_corrupt_rows": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i32), C.c_int, _f, C.c_int, _u64, _p, _p]),
+    "pyz_score_rows": (C.c_int, [_p, C.c_int, _i64, C.c_int, _p, C.c_int, _p, _p]),
     "pyz_sample_normal_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _u64, _u32, _u32, _p]),
     "pyz_sample_lowrank_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _f, _u64, _u32, _u32, _p]),
     "pyz_gather_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p]),

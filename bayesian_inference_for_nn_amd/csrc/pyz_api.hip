@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "pyz_common.h"
+#include "pyz_corrupt.h"
 #include "pyz_fused.h"
 #include "pyz_gemm.h"
 #include "pyz_gemm_ring.h"
@@ -2798,6 +2799,72 @@ int pyz_fill_normal(float *d_out, int64_t n, uint64_t seed, uint32_t stream_id, 
   if (!d_out || n <= 0) return pyz_fail(PYZ_E_INVALID, "bad output buffer");
   PYZ_LAUNCH(k_fill_normal, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, as_stream(stream), d_out, (long long)n,
                      seed, stream_id, step, mean, std);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- corrupted read-outs (no plan)
+int pyz_corrupt_rows(const float *d_x, int64_t n, int h, int w, int ch, int kind, const int32_t *severities, int n_sev,
+                     float pixel_max, int quantise, uint64_t seed, float *d_out, void *stream) {
+  if (kind < 0 || kind >= PYZ_CORRUPT_KINDS) return pyz_fail(PYZ_E_INVALID, "unknown corruption kind %d", kind);
+  if (!severities || n_sev < 1 || n_sev > PYZ_CORRUPT_MAX_SEV)
+    return pyz_fail(PYZ_E_INVALID, "n_sev %d outside 1..%d", n_sev, PYZ_CORRUPT_MAX_SEV);
+  if (n < 1 || n > INT_MAX || h < 1 || w < 1) return pyz_fail(PYZ_E_INVALID, "n, h and w must be positive (n below 2^31)");
+  CorruptArgs g{};
+  size_t lds = 0;
+  if (kind == PYZ_CORRUPT_REGRESSION) {
+    if (h != 1 || ch != 1) return pyz_fail(PYZ_E_INVALID, "the regression noise takes rows: h = ch = 1, the length as w");
+  } else {
+    if (ch != 1 && ch != 3) return pyz_fail(PYZ_E_INVALID, "ch %d: an image has 1 or 3 channels", ch);
+    if (!(pixel_max > 0.0f)) return pyz_fail(PYZ_E_INVALID, "pixel_max must be positive");
+    if ((long long)h * w > PYZ_LDS_BYTES / 24 || pyz_corrupt_lds(h, w) > PYZ_LDS_BYTES)
+      return pyz_fail(PYZ_E_INVALID, "a %d x %d image and its scratch copy (three channels each) do not fit %d KiB of LDS", h, w,
+                      PYZ_LDS_BYTES / 1024);
+    if (kind == PYZ_C_BLUR || kind == PYZ_C_CONTRAST || kind == PYZ_C_PIXELATE) lds = pyz_corrupt_lds(h, w);
+  }
+  g.kind = kind;
+  g.h = h;
+  g.w = w;
+  g.ch = ch;
+  g.planes = ch;
+  int rc = pyz_corrupt_tables(g, severities, n_sev);
+  if (rc) return rc;
+  if (!d_x || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  g.x = d_x;
+  g.out = d_out;
+  g.n = n;
+  g.pixel_max = pixel_max;
+  g.quantise = quantise ? 1 : 0;
+  g.out_scale = g.quantise ? pixel_max / 255.0f : pixel_max;
+  g.seed = seed;
+  if (lds > 64 * 1024)
+    PYZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_corrupt_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+  PYZ_LAUNCH(k_corrupt_rows, dim3((unsigned)n, (unsigned)n_sev), dim3(PYZ_CORRUPT_THREADS), lds, as_stream(stream), g);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_score_rows(const float *d_mean, int groups, int64_t n, int C, const void *d_y, int kind, void *d_out, void *stream) {
+  if (kind != 0 && kind != 1) return pyz_fail(PYZ_E_INVALID, "kind %d: 0 = classification, 1 = regression", kind);
+  if (groups < 1 || groups > 65535 || n < 1 || C < 1) return pyz_fail(PYZ_E_INVALID, "groups (at most 65535), n and C must be positive");
+  if (!d_mean || !d_y || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  if (kind == 0) {
+    PYZ_HIP(hipMemsetAsync(d_out, 0, sizeof(unsigned long long) * groups, st));
+    PYZ_LAUNCH(k_score_rows, dim3((unsigned)cdiv(n, 256), (unsigned)groups), dim3(256), 0, st, d_mean, (long long)n, C, d_y, 0,
+               static_cast<unsigned long long *>(d_out), (double *)nullptr);
+  } else {
+    const long long nblk = cdiv(n, PYZ_SCORE_ROWS_PER_BLOCK), total = (long long)groups * C;
+    if (total > INT_MAX || nblk > INT_MAX) return pyz_fail(PYZ_E_INVALID, "groups * C and the row blocks must stay below 2^31");
+    double *part = nullptr;   // the per-workgroup sums: stream-ordered scratch, gone when k_score_sum has read it
+    PYZ_HIP(hipMallocAsync((void **)&part, sizeof(double) * (size_t)total * (size_t)nblk, st));
+    PYZ_LAUNCH(k_score_rows, dim3((unsigned)nblk, (unsigned)groups), dim3(256), 0, st, d_mean, (long long)n, C, d_y, 1,
+               (unsigned long long *)nullptr, part);
+    PYZ_LAUNCH(k_score_sum, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, (const double *)part, (int)nblk, (int)total,
+               static_cast<double *>(d_out));
+    PYZ_HIP(hipFreeAsync(part, st));
+  }
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
 }

@@ -19,11 +19,16 @@
 #define PYZ_STREAM_PREDICT 4u  // weight draws of the read-outs, step = the draw's counter (tfd.take_device_draws); see below
 #define PYZ_STREAM_VADAM 5u  // VADAM weight perturbation (VADAM.py:59-65), step = the optimizer step
 #define PYZ_STREAM_BSAM 6u   // BSAM weight perturbation (BSAM.py:63-68), step = the optimizer step
+#define PYZ_STREAM_CORRUPT 7u  // noise of the image corruptions (visualisations/Robustness.py:10-38), step = 8 * kind + severity; see below
 // PYZ_STREAM_PREDICT, one draw (step) of a distribution over len elements:
 //   k_sample_normal_rows    z(e)  = element e, e < len
 //   k_sample_lowrank_rows   z1(e) = element e, e < len;  z2(c) = element 4 * ceil(len / 4) + c, c < k
 // z1 ends inside counter idx4 = ceil(len / 4) - 1 and z2 starts with counter idx4 = ceil(len / 4): the two never share a
 // counter, whatever len % 4 is.
+// PYZ_STREAM_CORRUPT (k_corrupt_rows, pyz_corrupt.h), image i, pixel (y, x), channel k of the REPLICATED three-channel tensor:
+//   element e = ((i h + y) w + x) 3 + k; the regression noise (kind 9) of element j of row i: e = i w + j
+//   gaussian / speckle / regression noise   z(e) = pyz_normal1 of element e
+//   shot / impulse noise                    the counter idx4 = e of its own: u or u0 = unit(word x), u1 = unit(word y)
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;

@@ -713,3 +713,52 @@ def gather_rows(out: torch.Tensor, col0: int, bank: torch.Tensor, idx):
     idx_d = torch.as_tensor(idx.astype(np.int32)).to(out.device)
     check(lib.pyz_gather_rows(ptr(out), out.shape[0], out.shape[1], int(col0), bank.shape[1], ptr(bank), bank.shape[0],
                               ptr(idx_d), _stream()))
+
+
+CORRUPTION_KINDS = 10          # PYZ_CORRUPT_KINDS: 0..8 the image corruptions of Robustness.py:10-93, 9 the regression noise
+
+
+def corrupt_rows(x: torch.Tensor, shape, kind: int, severities, pixel_max: float = 255.0, quantise: bool = True, seed: int = 0):
+    """(len(severities), n, row length) CUDA float32: the rows of x (n, h * w * ch) under corruption `kind` at every listed
+    severity (1..5), one launch (pyz_corrupt_rows).  shape = (h, w, ch), ch 1 or 3; kind 9 (x + c z on rows of any
+    length): shape = (1, row length, 1)."""
+    lib = _lib.load()
+    _f32(x, name="x")
+    h, w, ch = (int(v) for v in shape)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != h * w * ch:
+        raise ValueError(f"x must be (rows >= 1, {h * w * ch}) for shape {(h, w, ch)}, not {tuple(x.shape)}")
+    sev = [int(s) for s in severities]
+    if not 1 <= len(sev) <= 5 or any(not 1 <= s <= 5 for s in sev):
+        raise ValueError(f"severities must be one to five values in 1..5, not {sev}")
+    if not 0 <= int(kind) < CORRUPTION_KINDS:
+        raise ValueError(f"kind {kind} outside [0, {CORRUPTION_KINDS})")
+    out = torch.empty((len(sev), x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+    check(lib.pyz_corrupt_rows(ptr(x), x.shape[0], h, w, ch, int(kind), (C.c_int32 * len(sev))(*sev), len(sev),
+                               float(pixel_max), 1 if quantise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), _stream()))
+    return out
+
+
+def score_rows(mean: torch.Tensor, y: torch.Tensor, kind: int):
+    """Scores of `groups` read-outs mean (groups, n, C) (pyz_score_rows).  kind 0: y int32 (n,) labels -> int64 (groups,),
+    the rows whose predicted class (np.argmax; mean > 0.5 for C == 1) is wrong.  kind 1: y float32 (n, C) -> float64
+    (groups, C), the sums over rows of (mean - y)^2."""
+    lib = _lib.load()
+    _f32(mean, name="mean")
+    if mean.dim() != 3 or min(mean.shape) < 1:
+        raise ValueError(f"mean must be (groups, n, C), not {tuple(mean.shape)}")
+    groups, n, C_out = (int(v) for v in mean.shape)
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or not y.is_contiguous():
+        raise TypeError("y must be a contiguous CUDA(HIP) torch tensor")
+    if kind == 0:
+        if y.dtype != torch.int32 or y.numel() != n:
+            raise TypeError("labels must be CUDA int32, one per row")
+        out = torch.empty((groups,), dtype=torch.int64, device=mean.device)
+    elif kind == 1:
+        _f32(y, name="y")
+        if y.numel() != n * C_out:
+            raise ValueError("targets must be (rows, out)")
+        out = torch.empty((groups, C_out), dtype=torch.float64, device=mean.device)
+    else:
+        raise ValueError("kind must be 0 (classification) or 1 (regression)")
+    check(lib.pyz_score_rows(ptr(mean), groups, n, C_out, ptr(y), int(kind), ptr(out), _stream()))
+    return out

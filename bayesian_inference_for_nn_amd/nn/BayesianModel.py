@@ -164,8 +164,12 @@ class BayesianModel:
         MLPPlan.predict: device (mean (n, C), m2 (n, C, C) or None).  No sample tensor is formed."""
         import torch
         from ..engine import MLPPlan
-        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
+        if isinstance(x, torch.Tensor) and x.is_cuda:       # rows made on the device (corruption_scores) stay there
+            xd = x.to(torch.float32).reshape(len(x), -1).contiguous()
+        else:
+            x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
+            xd = None
         nb_samples = int(nb_samples)
         Wd = self.sample_weights_device(nb_samples)
         n = len(x)
@@ -174,7 +178,8 @@ class BayesianModel:
         chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
         if self._plan is None or self._plan.max_batch < rows or self._plan.max_particles < chunk_s:
             self._plan = MLPPlan(self._model.spec, max_batch=rows, max_particles=chunk_s)
-        xd = torch.as_tensor(x).cuda()
+        if xd is None:
+            xd = torch.as_tensor(x).cuda()
         C_out = int(self._model.dims[-1])
         mean_full = m2_full = None
         for r0 in range(0, n, rows):
@@ -203,6 +208,43 @@ class BayesianModel:
     def predictive_mean(self, x, nb_samples: int):
         """(n, C) NumPy float32: ``predict``'s mean alone (MLPPlan.predict without the sample tensor)."""
         return self._read_out(x, nb_samples, False)[0].cpu().numpy()
+
+    def corruption_scores(self, x, y, image_shape, kind: int, severities=(1, 2, 3, 4, 5), nb_samples: int = 100,
+                          regression: bool = False, pixel_max: float = 255.0, seed: int = 0):
+        """Per-severity error (NumPy float64, one entry per severity) of the Monte-Carlo mean prediction on the rows of x
+        under corruption `kind` (0..8 of Robustness.py:10-93 on images of image_shape = (h, w, ch); 9, the regression noise
+        of :16-19, on rows of any length): the fraction of rows wrong (classification, :253-254), or sklearn's
+        root_mean_squared_error, per output column, then their plain average (regression, :251).  The clean rows are
+        uploaded once; the len(severities) * n corrupted rows are made on the device (pyz_corrupt_rows), read out like
+        ``predict`` (the same row cap and workspace rule, fresh draws per call) and scored there (pyz_score_rows): no
+        image and no mean leaves the device."""
+        import torch
+        from .. import engine
+        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+        n = len(x)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(n, -1))
+        y = np.asarray(y.numpy() if hasattr(y, "numpy") else y)
+        if n < 1 or len(y) != n:
+            raise ValueError("x and y must hold the same, positive number of rows")
+        sev = [int(s) for s in severities]
+        C_out = int(self._model.dims[-1])
+        xd = torch.as_tensor(x).cuda()
+        if regression:
+            yd = torch.as_tensor(np.ascontiguousarray(y.astype(np.float32).reshape(n, -1))).cuda()
+            if yd.shape[1] != C_out:
+                raise ValueError(f"targets must be (rows, {C_out})")
+        else:
+            yd = torch.as_tensor(np.ascontiguousarray(y.reshape(-1).astype(np.int32))).cuda()
+        rows = engine.corrupt_rows(xd, image_shape, kind, sev, pixel_max=pixel_max, quantise=True, seed=seed)
+        # the moments form of the read-out: k_predict_moments normalises each draw's rows itself and keeps the sums in
+        # registers, where the mean-only form first has k_predict_rows write every normalised (draw, row) back for
+        # k_predict_mean to read again; the mean is the same bits (include/pyz.h), the second moment is dropped
+        mean, _ = self._read_out(rows.reshape(len(sev) * n, -1), nb_samples, True)
+        score = engine.score_rows(mean.reshape(len(sev), n, C_out).contiguous(), yd, 1 if regression else 0)
+        score = score.cpu().numpy().astype(np.float64)
+        if regression:
+            return np.sqrt(score / n).mean(axis=1)
+        return score / n
 
     def adversarial_examples(self, x, y, loss: str, epsilon: float, nb_samples: int):
         """(x_adv, x_grad) as NumPy arrays: x_grad = sum over nb_samples weight draws of the gradient of the draw's mean

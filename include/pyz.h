@@ -441,6 +441,49 @@ int pyz_predict_moments(pyz_mlp *mlp, const float *d_weights, int n_samples, con
 int pyz_input_grad(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, const void *d_y, int n,
                    float scale, float *d_xgrad, float epsilon, float *d_xadv, float *d_loss, void *stream);
 
+/* ---- R3: the corrupted inputs of Robustness.mean_corruption_error / corruption_error / robustness_by_corruption /
+ * corruption_robustness_by_severity (visualisations/Robustness.py:10-93 the corruption functions, :235-273 _error_rate,
+ * _corrupt, _corrupt_regression), made on the device without PIL or skimage.  No plan is needed.
+ * d_x (n, h, w, ch) float32, ch 1 or 3 -> d_out (n_sev, n, h * w * ch): block s holds severity severities[s] (a HOST
+ * array, values 1..5, n_sev <= 5), one launch for all of them.  v = x / pixel_max; a one-channel image is replicated to
+ * three channels (:260-266) and every kind works on three; c = the reference's table entry; clip is to [0, 1]:
+ *   0 gaussian_noise  clip(v + c z)
+ *   1 shot_noise      clip(K / c), K ~ Poisson(clip(v) c) by inversion from one uniform u:
+ *                     p = exp(-lam); s = p; k = 0; while (u > s && k < 255) { ++k; p *= lam / k; s += p; }
+ *   2 impulse_noise   skimage 's&p', salt_vs_pepper 0.5: flipped if u0 < c, then 1 if u1 < 0.5 else 0
+ *   3 speckle_noise   clip(v + v c z)
+ *   4 gaussian_blur   scipy.ndimage.gaussian_filter per channel, sigma = c, truncate 4, mode "nearest": radius
+ *                     r = int(4 c + 0.5), weights exp(-0.5 k^2 / c^2) / their sum, indices clamped to the image, axis 0
+ *                     then axis 1, taps summed from -r to r (r may exceed the image)
+ *   5 contrast        clip((v - m) c + m), m the channel's mean over the image
+ *   6 brightness      RGB -> HSV, V = clip(V + c), HSV -> RGB (skimage.color's formulas), clip
+ *   7 saturate        RGB -> HSV, S = clip(S c0 + c1), HSV -> RGB, clip
+ *   8 pixelate        PIL BOX down to (max(1, int(h c)), max(1, int(w c))), horizontal pass then vertical, NEAREST back up,
+ *                     in float.  BOX along an axis of length in -> out: scale = in / out, center = (i + 0.5) scale,
+ *                     lo = max(0, int(center - scale / 2 + 0.5)), hi = min(in, int(center + scale / 2 + 0.5)), source j in
+ *                     [lo, hi) has weight 1 if -0.5 < (j - center + 0.5) / scale <= 0.5, normalised by the sum (float64
+ *                     decisions).  NEAREST: source index min(small - 1, int((i + 0.5) small / in))
+ *   9 gaussian_noise_regression  x + c z on every element of a row of any length: pass the length as w, h = ch = 1; no
+ *                     replication, clip or quantisation, pixel_max is ignored
+ * Kinds 0..8 with quantise = 1: each channel becomes the level floor(255 value) (np.uint8 at :270), a one-channel input
+ * takes the mean of its three levels (:246), the result is multiplied by pixel_max / 255 -- with pixel_max = 255 the
+ * reference's numbers.  quantise = 0: the value (or the channel mean of the values) times pixel_max, without the floor.
+ * Noise: Philox stream PYZ_STREAM_CORRUPT (csrc/pyz_rng.h), step = 8 kind + severity, element ((i h + y) w + x) 3 + k of
+ * the replicated tensor (kind 9: i w + j): a function of (seed, kind, severity, element) alone, so one severity called
+ * alone gives the bits it has in a call with five.  PYZ_E_INVALID, with no device touched: ch outside {1, 3}, a severity
+ * outside 1..5, n_sev outside 1..5, an unknown kind, an image whose two three-channel copies (2 * 3 * h * w floats, plus the
+ * kernel's reduction row and pixelate's tap table) exceed the 160 KiB of LDS (64 x 64 fits). */
+int pyz_corrupt_rows(const float *d_x, int64_t n, int h, int w, int ch, int kind, const int32_t *severities, int n_sev,
+                     float pixel_max, int quantise, uint64_t seed, float *d_out, void *stream);
+
+/* The scores of such read-outs (met.accuracy_score / met.root_mean_squared_error at Robustness.py:250-254), for `groups`
+ * blocks of n rows at once: d_mean (groups, n, C) float32, the mean predictions.
+ *   kind 0, classification: d_y int32[n] labels shared by every group; d_out int64[groups] = the rows whose predicted class
+ *     differs from the label.  Predicted class: the first index of the maximum for C >= 2 (np.argmax), mean > 0.5 for C == 1.
+ *   kind 1, regression: d_y float32 (n, C); d_out double[groups * C] = the sum over rows of (mean - y)^2, float64 sums per
+ *     workgroup added in workgroup order (no floating-point atomics: the same bits on every call). */
+int pyz_score_rows(const float *d_mean, int groups, int64_t n, int C, const void *d_y, int kind, void *d_out, void *stream);
+
 /* ---- noise: d_out[i] = mean + std * z_i, z from Philox stream (seed, stream, step).
  * (tf.random.normal at SGLD.py:67, HMC.py:171; tfp samplers at BBB.py:234-237,
  * SVGD.py:154, distributions/tf/TensorflowProbabilityDistribution.py:55-58.) */
