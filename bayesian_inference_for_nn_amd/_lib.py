@@ -78,6 +78,8 @@ SIGNATURES = {
     "pyz_svgd_combine": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _f, _f, _i64, _p, _p]),
     "pyz_predict": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
     "pyz_predict_moments": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
+    "pyz_grid_rows": (C.c_int, [_p, C.c_int, _f, _f, C.c_int, _f, _f, C.c_int, _i64, _i64, _p, _p]),
+    "pyz_predict_surface": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
     "pyz_input_grad": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, _f, _p, _f, _p, _p, _p]),
     "pyz_corrupt_rows": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i32), C.c_int, _f, C.c_int, _u64, _p, _p]),
     "pyz_score_rows": (C.c_int, [_p, C.c_int, _i64, C.c_int, _p, C.c_int, _p, _p]),

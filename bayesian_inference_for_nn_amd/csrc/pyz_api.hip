@@ -16,6 +16,7 @@
 #include "pyz_input_grad.h"
 #include "pyz_kernels.h"
 #include "pyz_predict_moments.h"
+#include "pyz_surface.h"
 #include "pyz_rng.h"
 #include "pyz_sgld_chains.h"
 
@@ -2704,6 +2705,59 @@ int pyz_predict_moments(pyz_mlp *m, const float *d_weights, int n_samples, const
     launch_forward(m, d_weights + (long long)s0 * m->D, m->D, g.S, d_x, nullptr, n, m->ctl, st);
     if (!pyz_launch_predict_moments(g, st))
       return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the moments kernel's LDS", g.C);
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- decision surfaces (Plotter)
+int pyz_grid_rows(const float *d_basis, int d, float a0, float da, int n1, float b0, float db, int n2, int64_t row0,
+                  int64_t n, float *d_out, void *stream) {
+  if (n1 < 1 || n2 < 1 || d < 1) return pyz_fail(PYZ_E_INVALID, "n1, n2 and d must be positive");
+  const int64_t total = (int64_t)n1 * n2;
+  if (row0 < 0 || n < 1 || row0 > total || n > total - row0)
+    return pyz_fail(PYZ_E_INVALID, "rows [%lld, %lld) outside the %d x %d grid", (long long)row0, (long long)(row0 + n), n1, n2);
+  if (!d_basis || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  const long long n_out = (long long)n * d;
+  if (cdiv(n_out, 256) > 0x7fffffffLL) return pyz_fail(PYZ_E_INVALID, "too many rows for one call: split the row range");
+  PYZ_LAUNCH(k_grid_rows, dim3((unsigned)cdiv(n_out, 256)), dim3(256), 0, as_stream(stream), d_basis, d, a0, da, b0, db, n2,
+             (long long)row0, n_out, d_out);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_predict_surface(pyz_mlp *m, const float *d_weights, int n_samples, const float *d_x, int n, int column,
+                        float *d_cols, float *d_mean, float *d_top, int32_t *d_cls, float *d_ent, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_samples < 1 || n < 1) return pyz_fail(PYZ_E_INVALID, "n_samples and n must be positive");
+  if (n > m->max_batch) return pyz_fail(PYZ_E_SHAPE, "n %d exceeds the plan's max_batch %d", n, m->max_batch);
+  PredictSurfaceArgs g{};
+  g.C = m->dims[m->L];
+  if (column < 0 || column >= g.C) return pyz_fail(PYZ_E_INVALID, "column %d outside [0, %d)", column, g.C);
+  if (!d_weights || !d_x || !d_mean) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (!pyz_predict_surface_fits(g.C))
+    return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the surface kernel's LDS", g.C);
+  hipStream_t st = as_stream(stream);
+  int rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st);
+  if (rc) return rc;
+  g.last = m->act[m->L - 1];
+  g.pstride = (long long)m->max_batch * g.C;
+  g.softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
+  g.n = n;
+  g.column = column;
+  g.mean = d_mean;
+  g.top = d_top;
+  g.cls = d_cls;
+  g.ent = d_ent;
+  g.inv_total = 1.0f / (float)n_samples;
+  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
+    g.S = std::min(m->max_p, n_samples - s0);
+    g.accumulate = s0 > 0 ? 1 : 0;
+    g.finish = s0 + g.S >= n_samples && (d_top || d_cls || d_ent) ? 1 : 0;
+    g.cols = d_cols ? d_cols + (long long)s0 * n : nullptr;
+    launch_forward(m, d_weights + (long long)s0 * m->D, m->D, g.S, d_x, nullptr, n, m->ctl, st);
+    if (!pyz_launch_predict_surface(g, st))
+      return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the surface kernel's LDS", g.C);
   }
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;

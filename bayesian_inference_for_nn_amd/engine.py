@@ -606,6 +606,34 @@ class MLPPlan:
                                            _stream()))
         return mean, m2
 
+    def predict_surface(self, weights, x, column=0, want_cols=True, want_summary=True):
+        """(cols, mean, top, cls, ent) of the draws `weights` (S, D) on the rows of x, for decision-surface plots:
+        cols (S, n) = column `column` of every draw's prediction (None without want_cols), mean (n, out) = predict's mean
+        bit for bit, and of each mean row q (one output: the pair (1 - m, m)) top (n,) = max q, cls (n,) int32 = its
+        first index, ent (n,) = -sum q log(q + 1e-5), raw (all None without want_summary).  One kernel per chunk of
+        max_particles draws (pyz_predict_surface); the (S, n, out) sample tensor is never formed."""
+        _f32(weights, name="weights")
+        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
+            raise ValueError(f"weights must be (draws >= 1, {self.D})")
+        _f32(x, name="x")
+        if x.dim() != 2 or x.shape[1] != self.spec.dims[0] or x.shape[0] < 1:
+            raise ValueError(f"x must be (rows >= 1, {self.spec.dims[0]})")
+        S, n, C_out = int(weights.shape[0]), int(x.shape[0]), self.spec.dims[-1]
+        if n > self.max_batch:
+            raise ValueError(f"{n} rows exceed the plan's max_batch {self.max_batch}")
+        column = int(column)
+        if not 0 <= column < C_out:
+            raise ValueError(f"column {column} outside [0, {C_out})")
+        dev = self.device
+        cols = torch.empty((S, n), dtype=torch.float32, device=dev) if want_cols else None
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=dev)
+        top = torch.empty((n,), dtype=torch.float32, device=dev) if want_summary else None
+        cls = torch.empty((n,), dtype=torch.int32, device=dev) if want_summary else None
+        ent = torch.empty((n,), dtype=torch.float32, device=dev) if want_summary else None
+        check(self.lib.pyz_predict_surface(self.h, ptr(weights), S, ptr(x), n, column, ptr(cols), ptr(mean), ptr(top),
+                                           ptr(cls), ptr(ent), _stream()))
+        return cols, mean, top, cls, ent
+
     # ------------------------------------------------------------------ R2
     def input_grad(self, weights, x, y, scale=1.0, epsilon=None):
         """(xgrad, xadv or None, losses): xgrad (n, in) = scale * sum over the draws `weights` (S, D) of the gradient of
@@ -713,6 +741,26 @@ def gather_rows(out: torch.Tensor, col0: int, bank: torch.Tensor, idx):
     idx_d = torch.as_tensor(idx.astype(np.int32)).to(out.device)
     check(lib.pyz_gather_rows(ptr(out), out.shape[0], out.shape[1], int(col0), bank.shape[1], ptr(bank), bank.shape[0],
                               ptr(idx_d), _stream()))
+
+
+def grid_rows(basis: torch.Tensor, a0: float, da: float, n1: int, b0: float, db: float, n2: int, row0: int = 0, n=None):
+    """(n, d) CUDA float32: rows [row0, row0 + n) of the n1 x n2 grid ('ij' order: row r is (r // n2, r % n2)) with
+    u = a0 + i * da, v = b0 + j * db, mapped to input space as u * basis[:, 0] + v * basis[:, 1]; basis is a CUDA (d, 2)
+    matrix.  Every operation is rounded to float32 on its own (pyz_grid_rows)."""
+    lib = _lib.load()
+    _f32(basis, name="basis")
+    if basis.dim() != 2 or basis.shape[1] != 2 or basis.shape[0] < 1:
+        raise ValueError(f"basis must be (d >= 1, 2), not {tuple(basis.shape)}")
+    n1, n2, row0 = int(n1), int(n2), int(row0)
+    if n1 < 1 or n2 < 1:
+        raise ValueError(f"the grid must be at least 1 x 1, not {n1} x {n2}")
+    n = n1 * n2 - row0 if n is None else int(n)
+    if row0 < 0 or n < 1 or row0 + n > n1 * n2:
+        raise ValueError(f"rows [{row0}, {row0 + n}) outside the {n1} x {n2} grid")
+    out = torch.empty((n, basis.shape[0]), dtype=torch.float32, device=basis.device)
+    check(lib.pyz_grid_rows(ptr(basis), int(basis.shape[0]), float(a0), float(da), n1, float(b0), float(db), n2, row0, n,
+                            ptr(out), _stream()))
+    return out
 
 
 CORRUPTION_KINDS = 10          # PYZ_CORRUPT_KINDS: 0..8 the image corruptions of Robustness.py:10-93, 9 the regression noise

@@ -117,23 +117,28 @@ class BayesianModel:
     # ------------------------------------------------------------------ read-out
     _predict_rows_cap = 16384      # rows per launch sequence of predict (more rows: several sequences, results joined on the device)
 
-    def predict(self, x, nb_samples: int, y_true=None, loss_func=None):
-        """(list of per-sample outputs, their mean); NaN outputs count as 0 (BayesianModel.py:106-129)."""
-        import torch
+    def _read_out_plan(self, n: int, nb_samples: int) -> int:
+        """Rows per launch sequence of a read-out of n rows and nb_samples draws; self._plan serves them afterwards.
+        Bounds the activation workspace: rows x samples per launch (the plan keeps an activation and a delta buffer per
+        layer: 2 * sum(widths) floats per (sample, row)).  2^29 floats = 2 GiB of the 288: 100 draws x 10 000 rows of the
+        784 -> 200 -> 10 model go out as ONE launch per layer (3.35 ms for the wide layer against 7 x 0.61 ms in seven)."""
         from ..engine import MLPPlan
-        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))   # (no copy of float32 input)
-        nb_samples = int(nb_samples)
-        Wd = self.sample_weights_device(nb_samples)
-        n = len(x)
-        # bound the activation workspace: rows x samples per launch (the plan keeps an activation and a delta buffer per
-        # layer: 2 * sum(widths) floats per (sample, row)).  2^29 floats = 2 GiB of the 288: 100 draws x 10 000 rows of the
-        # 784 -> 200 -> 10 model go out as ONE launch per layer (3.35 ms for the wide layer against 7 x 0.61 ms in seven)
         rows = min(n, int(self._predict_rows_cap))
         per = 2 * sum(int(d) for d in self._model.dims[1:])
         chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
         if self._plan is None or self._plan.max_batch < rows or self._plan.max_particles < chunk_s:
             self._plan = MLPPlan(self._model.spec, max_batch=rows, max_particles=chunk_s)
+        return rows
+
+    def predict(self, x, nb_samples: int, y_true=None, loss_func=None):
+        """(list of per-sample outputs, their mean); NaN outputs count as 0 (BayesianModel.py:106-129)."""
+        import torch
+        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))   # (no copy of float32 input)
+        nb_samples = int(nb_samples)
+        Wd = self.sample_weights_device(nb_samples)
+        n = len(x)
+        rows = self._read_out_plan(n, nb_samples)
         xd = torch.as_tensor(x).cuda()
         C_out = int(self._model.dims[-1])
         full = mean_full = None
@@ -163,7 +168,6 @@ class BayesianModel:
         """predict's draws, row cap and workspace rule; per row chunk MLPPlan.predict_moments (moments) or the mean-only
         MLPPlan.predict: device (mean (n, C), m2 (n, C, C) or None).  No sample tensor is formed."""
         import torch
-        from ..engine import MLPPlan
         if isinstance(x, torch.Tensor) and x.is_cuda:       # rows made on the device (corruption_scores) stay there
             xd = x.to(torch.float32).reshape(len(x), -1).contiguous()
         else:
@@ -173,11 +177,7 @@ class BayesianModel:
         nb_samples = int(nb_samples)
         Wd = self.sample_weights_device(nb_samples)
         n = len(x)
-        rows = min(n, int(self._predict_rows_cap))
-        per = 2 * sum(int(d) for d in self._model.dims[1:])
-        chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
-        if self._plan is None or self._plan.max_batch < rows or self._plan.max_particles < chunk_s:
-            self._plan = MLPPlan(self._model.spec, max_batch=rows, max_particles=chunk_s)
+        rows = self._read_out_plan(n, nb_samples)
         if xd is None:
             xd = torch.as_tensor(x).cuda()
         C_out = int(self._model.dims[-1])
@@ -208,6 +208,63 @@ class BayesianModel:
     def predictive_mean(self, x, nb_samples: int):
         """(n, C) NumPy float32: ``predict``'s mean alone (MLPPlan.predict without the sample tensor)."""
         return self._read_out(x, nb_samples, False)[0].cpu().numpy()
+
+    def _surface(self, n, nb_samples, column, want_cols, rows_of):
+        """The read-out behind predictive_surface / grid_surface: predict's draws, row cap and workspace rule; per row
+        chunk ``rows_of(r0, count)`` hands the device rows and MLPPlan.predict_surface reads them out.  NumPy
+        (cols (S, n) or None, mean (n, C), top (n,), cls (n,) int32, ent (n,))."""
+        import torch
+        nb_samples, n = int(nb_samples), int(n)
+        if n < 1 or nb_samples < 1:
+            raise ValueError("rows and nb_samples must be positive")
+        C_out = int(self._model.dims[-1])
+        if not 0 <= int(column) < C_out:
+            raise ValueError(f"column {column} outside [0, {C_out})")
+        Wd = self.sample_weights_device(nb_samples)
+        rows = self._read_out_plan(n, nb_samples)
+        dev = Wd.device
+        cols = torch.empty((nb_samples, n), dtype=torch.float32, device=dev) if want_cols else None
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=dev)
+        top = torch.empty((n,), dtype=torch.float32, device=dev)
+        cls = torch.empty((n,), dtype=torch.int32, device=dev)
+        ent = torch.empty((n,), dtype=torch.float32, device=dev)
+        for r0 in range(0, n, rows):
+            c, m, t, k, e = self._plan.predict_surface(Wd, rows_of(r0, min(rows, n - r0)), column=column, want_cols=want_cols)
+            if want_cols:
+                cols[:, r0:r0 + rows] = c
+            mean[r0:r0 + rows], top[r0:r0 + rows], cls[r0:r0 + rows], ent[r0:r0 + rows] = m, t, k, e
+        self._model.set_flat(Wd[-1].cpu().numpy())      # the reference leaves the last draw assigned
+        return (cols.cpu().numpy() if want_cols else None, mean.cpu().numpy(), top.cpu().numpy(), cls.cpu().numpy(),
+                ent.cpu().numpy())
+
+    def predictive_surface(self, x, nb_samples: int, column: int = 0, want_cols: bool = False):
+        """(cols, mean, top, cls, ent) as NumPy arrays for the rows of x: mean (n, C) = ``predict``'s mean (bit for bit,
+        for the same draws); of each mean row q (one output: the pair (1 - m, m)) top = max q, cls = argmax q (int32),
+        ent = -sum q log(q + 1e-5) in float32, raw; cols (nb_samples, n) = column `column` of every draw's prediction, or
+        None.  Computed on the device by pyz_predict_surface: the sample tensor is neither written nor copied."""
+        import torch
+        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+        xd = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))).cuda()
+        return self._surface(len(x), nb_samples, column, want_cols, lambda r0, cnt: xd[r0:r0 + cnt].contiguous())
+
+    def grid_surface(self, basis, a0, da, n1, b0, db, n2, nb_samples: int, column: int = 0, want_cols: bool = False):
+        """``predictive_surface`` on the n1 x n2 grid u_i = a0 + i da, v_j = b0 + j db ('ij' row order), each grid point
+        mapped to input space as u * basis[:, 0] + v * basis[:, 1] (basis (d, 2): the identity for a 2-D input, the PCA
+        axes otherwise).  The weights are drawn once; the grid is walked in row chunks under predict's row cap and
+        workspace rule, each chunk's rows made on the device (pyz_grid_rows) and read out there (pyz_predict_surface):
+        no grid row and no sample tensor reaches the host.  NumPy: cols (nb_samples, n1 * n2) or None, mean, top, cls,
+        ent."""
+        import torch
+        from .. import engine
+        basis = np.ascontiguousarray(np.asarray(basis, dtype=np.float32))
+        if basis.ndim != 2 or basis.shape != (int(self._model.dims[0]), 2):
+            raise ValueError(f"basis must be ({int(self._model.dims[0])}, 2), not {basis.shape}")
+        n1, n2 = int(n1), int(n2)
+        if n1 < 1 or n2 < 1:
+            raise ValueError(f"the grid must be at least 1 x 1, not {n1} x {n2}")
+        bd = torch.as_tensor(basis).cuda()
+        return self._surface(n1 * n2, nb_samples, column, want_cols,
+                             lambda r0, cnt: engine.grid_rows(bd, a0, da, n1, b0, db, n2, r0, cnt))
 
     def corruption_scores(self, x, y, image_shape, kind: int, severities=(1, 2, 3, 4, 5), nb_samples: int = 100,
                           regression: bool = False, pixel_max: float = 255.0, seed: int = 0):

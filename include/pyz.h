@@ -431,6 +431,32 @@ int pyz_predict(pyz_mlp *mlp, const float *d_weights, int n_samples, const float
 int pyz_predict_moments(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, int n,
                         float *d_mean, float *d_m2, void *stream);
 
+/* ---- decision surfaces: what Plotter.plot_decision_boundaries / plot_uncertainty_area (visualisations/Plotter.py:54-78,
+ * 100-135) need of a read-out on a dense 2-D grid, made and kept on the device.
+ *
+ * pyz_grid_rows writes rows [row0, row0 + n) of the n1 x n2 grid, mapped back to input space.  No plan is needed.  Row r
+ * has i = r / n2, j = r % n2 (tf.meshgrid(indexing='ij') then reshape(-1), :132-133), u = a0 + (float)i * da,
+ * v = b0 + (float)j * db, and d_out[r - row0][k] = u * B[k][0] + v * B[k][1] with B = d_basis, (d, 2) float32 row-major
+ * (grid @ base_matrix^T, :134).  Every product and sum is rounded to float32 on its own (no contraction): a NumPy float32
+ * restatement is equal bit for bit.  PYZ_E_INVALID, before the device is touched: a null pointer, n1 < 1, n2 < 1, d < 1,
+ * n < 1, a row range outside the grid. */
+int pyz_grid_rows(const float *d_basis, int d, float a0, float da, int n1, float b0, float db, int n2, int64_t row0,
+                  int64_t n, float *d_out, void *stream);
+
+/* The read-out of pyz_predict, keeping only (p = pyz_predict's sample value: softmax where the last activation is
+ * softmax, NaN -> 0, never written):
+ *   d_cols (n_samples, n), optional: d_cols[s][j] = p[s][j][column], bit for bit;
+ *   d_mean (n, out), required (it carries the sums across chunks of draws): pyz_predict's mean, bit for bit;
+ *   d_top float[n], d_cls int32[n], d_ent float[n], each optional, functions of the finished mean row q (out == 1: the
+ *   pair (1 - m, m), the subtraction in float32, Plotter.py:37-39,49-51,68-70): top = max_a q_a, cls = the first index of
+ *   the maximum (np.argmax), ent = -sum_a q_a * logf(q_a + 1e-5f), a sequential float32 sum in column order with every
+ *   product and sum rounded on its own (:366), written raw: nan_to_num is the host's.
+ * One kernel per chunk of max_particles draws, in place of pyz_predict's two; the bits do not depend on the chunking.
+ * Rows >= n of no output are written.  n <= max_batch (PYZ_E_SHAPE); column in [0, out), n_samples >= 1, the required
+ * pointers non-null (PYZ_E_INVALID); out beyond ~13 600 (a row no longer fits a compute unit's LDS): PYZ_E_SHAPE. */
+int pyz_predict_surface(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, int n, int column,
+                        float *d_cols, float *d_mean, float *d_top, int32_t *d_cls, float *d_ent, void *stream);
+
 /* ---- R2: the input gradient of Robustness.adversarial_robustness (visualisations/Robustness.py:115-144):
  * d_xgrad (n, dims[0]) = scale * sum_s d loss_s / d x over the n_samples draws d_weights (n_samples, D), loss_s =
  * draw s's mean loss over the n contiguous rows of d_x (no row gather; d_y as for pyz_mlp_loss_grad), summed inside
