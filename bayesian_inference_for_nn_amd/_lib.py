@@ -14,6 +14,8 @@ SWEEP = {"gauss_seidel": 0, "jacobi": 1}
 GAMMA_MEDIAN = -1.0       # PYZ_SVGD_GAMMA_MEDIAN
 
 STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM, STREAM_BSAM, STREAM_CORRUPT = 0, 1, 2, 3, 4, 5, 6, 7
+STREAM_PILCO = 8           # PYZ_STREAM_PILCO
+REWARD = {"Cart": 0, "Acb 2 factors": 1}    # PYZ_REWARD_*; the names of dynamics.all_rewards
 
 
 class PyzError(RuntimeError):
@@ -83,6 +85,12 @@ SIGNATURES = {
     "pyz_input_grad": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, _f, _p, _f, _p, _p, _p]),
     "pyz_corrupt_rows": (C.c_int, [_p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i32), C.c_int, _f, C.c_int, _u64, _p, _p]),
     "pyz_score_rows": (C.c_int, [_p, C.c_int, _i64, C.c_int, _p, C.c_int, _p, _p]),
+    "pyz_pilco_create": (C.c_int, [C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int,
+                                   C.c_int, C.POINTER(_p)]),
+    "pyz_pilco_destroy": (C.c_int, [_p]),
+    "pyz_pilco_workspace_bytes": (_i64, [_p]),
+    "pyz_pilco_policy_step": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _p, C.c_int, C.c_int, _f, C.c_int, _f, _p, _p, _p, _p,
+                                        C.c_int, _p]),
     "pyz_sample_normal_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _u64, _u32, _u32, _p]),
     "pyz_sample_lowrank_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _f, _u64, _u32, _u32, _p]),
     "pyz_gather_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p]),

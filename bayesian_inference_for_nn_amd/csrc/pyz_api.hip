@@ -14,6 +14,7 @@
 #include "pyz_hmc_fused.h"
 #include "pyz_hmc_multi.h"
 #include "pyz_input_grad.h"
+#include "pyz_pilco.h"
 #include "pyz_kernels.h"
 #include "pyz_predict_moments.h"
 #include "pyz_surface.h"
@@ -2921,6 +2922,193 @@ int pyz_score_rows(const float *d_mean, int groups, int64_t n, int C, const void
   }
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- D1: Deep-PILCO policy update (pyz_pilco.h)
+struct pyz_pilco {
+  PilcoArgs a{};                 // the nets, K, S, A and the workspace pointers; the per-call fields are filled by each call
+  int max_h = 0;
+  void *ws = nullptr;            // one allocation: the tape, the state gradients, the partial rows, the call's scalars
+  size_t ws_bytes = 0;
+  float *st_own = nullptr, *ac_own = nullptr;   // states / actions when the caller does not ask for them
+  PilcoCtl *ctl = nullptr;
+  PyzGraphCache<4> graphs;       // one graph per (H, freq); everything else baked into them is the cache's key
+};
+
+static int pilco_net(PilcoNet &net, const char *what, int L, const int32_t *dims, const int32_t *acts, bool softmax_last) {
+  if (!dims || !acts) return pyz_fail(PYZ_E_INVALID, "null argument");
+  if (L < 1 || L > PILCO_MAX_LAYERS) return pyz_fail(PYZ_E_INVALID, "%s: %d layers outside [1, %d]", what, L, PILCO_MAX_LAYERS);
+  net.L = L;
+  int off = 0;
+  for (int l = 0; l <= L; ++l) {
+    if (dims[l] < 1 || dims[l] > PILCO_MAX_WIDTH)
+      return pyz_fail(PYZ_E_INVALID, "%s: dims[%d] = %d outside [1, %d]", what, l, dims[l], PILCO_MAX_WIDTH);
+    net.dims[l] = dims[l];
+  }
+  for (int l = 0; l < L; ++l) {
+    const bool last = l == L - 1;
+    if (acts[l] < PYZ_ACT_LINEAR || acts[l] > PYZ_ACT_SOFTMAX || (acts[l] == PYZ_ACT_SOFTMAX && !(last && softmax_last)))
+      return pyz_fail(PYZ_E_INVALID, "%s: activation %d at layer %d is not supported", what, acts[l], l);
+    net.acts[l] = acts[l];
+    net.w_off[l] = off;
+    off += (dims[l] + 1) * dims[l + 1];
+  }
+  return PYZ_OK;
+}
+
+int pyz_pilco_create(int n_policy_layers, const int32_t *h_policy_dims, const int32_t *h_policy_acts, int n_dynamics_layers,
+                     const int32_t *h_dynamics_dims, const int32_t *h_dynamics_acts, int particles, int max_horizon,
+                     pyz_pilco **out) {
+  if (!out) return pyz_fail(PYZ_E_INVALID, "null argument");
+  *out = nullptr;
+  PilcoArgs a{};
+  int rc;
+  if ((rc = pilco_net(a.pol, "policy", n_policy_layers, h_policy_dims, h_policy_acts, true))) return rc;
+  if ((rc = pilco_net(a.dyn, "dynamics", n_dynamics_layers, h_dynamics_dims, h_dynamics_acts, false))) return rc;
+  if (a.dyn.acts[a.dyn.L - 1] != PYZ_ACT_LINEAR)
+    return pyz_fail(PYZ_E_INVALID, "the dynamics' last layer must be linear, not activation %d", a.dyn.acts[a.dyn.L - 1]);
+  if (particles < 2 || particles > PILCO_MAX_K)
+    return pyz_fail(PYZ_E_INVALID, "%d particles outside [2, %d] (one particle has deviation 0 and a NaN gradient)", particles, PILCO_MAX_K);
+  if (max_horizon < 1 || max_horizon > PILCO_MAX_H) return pyz_fail(PYZ_E_INVALID, "max_horizon %d outside [1, %d]", max_horizon, PILCO_MAX_H);
+  const int S = a.pol.dims[0], A = a.pol.dims[a.pol.L];
+  if (S + A > PILCO_MAX_IN) return pyz_fail(PYZ_E_INVALID, "S + A = %d exceeds %d", S + A, PILCO_MAX_IN);
+  if (a.dyn.dims[0] != S + A || a.dyn.dims[a.dyn.L] != S)
+    return pyz_fail(PYZ_E_INVALID, "dynamics dims (%d -> %d) do not fit the policy's (S = %d, A = %d): expected %d -> %d",
+                    a.dyn.dims[0], a.dyn.dims[a.dyn.L], S, A, S + A, S);
+  const int K = particles;
+  a.K = K;
+  a.S = S;
+  a.A = A;
+  a.Dp = a.pol.w_off[a.pol.L - 1] + (long long)(a.pol.dims[a.pol.L - 1] + 1) * A;
+  a.Dd = a.dyn.w_off[a.dyn.L - 1] + (long long)(a.dyn.dims[a.dyn.L - 1] + 1) * S;
+  a.maxw = PILCO_MAX_IN;
+  for (int l = 0; l <= a.pol.L; ++l) a.maxw = std::max(a.maxw, a.pol.dims[l]);
+  for (int l = 0; l <= a.dyn.L; ++l) a.maxw = std::max(a.maxw, a.dyn.dims[l]);
+  for (int l = 1; l < a.pol.L; ++l) a.tw_pol += a.pol.dims[l];
+  a.tw = a.tw_pol;
+  for (int l = 1; l < a.dyn.L; ++l) a.tw += a.dyn.dims[l];
+  a.pw = S + a.tw_pol + A;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return pyz_fail(PYZ_E_NODEV, "no HIP device visible");
+
+  // workspace, in floats (each block rounded up to 64): y H K S + states (H + 1) K S + actions H K A + tape H K tw +
+  // (m, sd) 2 H S + state gradients 2 K S + rewards (H + 1) K + cost factors H + 1 + partial rows K D_pol +
+  // transposed kernels K D_dyn + D_pol + 64 for the scalars
+  const size_t Hm = (size_t)max_horizon, KS = (size_t)K * S;
+  const size_t n[] = {Hm * KS, (Hm + 1) * KS, Hm * K * A, Hm * K * (size_t)a.tw, 2 * Hm * S, 2 * KS, (Hm + 1) * K, Hm + 1,
+                      (size_t)K * (size_t)a.Dp, (size_t)K * (size_t)a.Dd, (size_t)a.Dp, 64};
+  size_t total = 0;
+  for (size_t v : n) total += (v + 63) & ~(size_t)63;
+  pyz_pilco *p = new pyz_pilco();
+  p->ws_bytes = total * sizeof(float);
+  if (hipMalloc(&p->ws, p->ws_bytes) != hipSuccess) {
+    const size_t bytes = p->ws_bytes;
+    delete p;
+    return pyz_fail(PYZ_E_OOM, "workspace allocation of %zu bytes failed", bytes);
+  }
+  float *base = static_cast<float *>(p->ws);
+  float **slot[] = {&a.y, &p->st_own, &p->ac_own, &a.tape, &a.msd, &a.g, &a.rew, &a.coef, &a.part, &a.WT, &a.phiT};
+  for (int q = 0; q < 11; ++q) {
+    *slot[q] = base;
+    base += (n[q] + 63) & ~(size_t)63;
+  }
+  p->ctl = reinterpret_cast<PilcoCtl *>(base);
+  a.ctl = p->ctl;
+  p->a = a;
+  p->max_h = max_horizon;
+  const size_t lds = std::max(pilco_fwd_lds(K, S, a.maxw), pilco_bwd_lds(K, S, a.maxw, a.pw));
+  if (lds > 160 * 1024) {
+    pyz_pilco_destroy(p);
+    return pyz_fail(PYZ_E_INVALID, "the step kernels would need %zu bytes of LDS", lds);
+  }
+  if (lds > 64 * 1024)
+    for (const void *k : {reinterpret_cast<const void *>(k_pilco_fwd), reinterpret_cast<const void *>(k_pilco_tail),
+                          reinterpret_cast<const void *>(k_pilco_bwd)})
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        pyz_pilco_destroy(p);
+        return pyz_fail(PYZ_E_HIP, "hipFuncSetAttribute(k_pilco_*) failed");
+      }
+  *out = p;
+  return PYZ_OK;
+}
+
+int pyz_pilco_destroy(pyz_pilco *p) {
+  if (!p) return PYZ_OK;
+  p->graphs.drop();
+  if (p->ws) (void)hipFree(p->ws);
+  delete p;
+  return PYZ_OK;
+}
+
+int64_t pyz_pilco_workspace_bytes(const pyz_pilco *p) { return p ? (int64_t)p->ws_bytes : -1; }
+
+int pyz_pilco_policy_step(pyz_pilco *p, float *d_phi, float *d_m, float *d_v, int64_t adam_t, const float *d_W,
+                          const float *d_s0, const float *d_eps, int H, int freq, float gamma, int reward, float lr,
+                          float *d_cost, float *d_grad, float *d_states, float *d_actions, int use_graph, void *stream) {
+  if (!p) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (H < 1 || H > p->max_h) return pyz_fail(PYZ_E_SHAPE, "horizon %d outside [1, %d] of the plan", H, p->max_h);
+  if (freq < 1) return pyz_fail(PYZ_E_INVALID, "freq %d must be >= 1", freq);
+  if (reward != PYZ_REWARD_CART && reward != PYZ_REWARD_ACB) return pyz_fail(PYZ_E_INVALID, "unknown reward %d", reward);
+  const int need = reward == PYZ_REWARD_CART ? 4 : 5;
+  if (p->a.S < need) return pyz_fail(PYZ_E_INVALID, "reward %d reads %d state entries, the state has %d", reward, need, p->a.S);
+  if (adam_t < 0) return pyz_fail(PYZ_E_INVALID, "adam_t %lld must be >= 0", (long long)adam_t);
+  if (!d_phi || !d_W || !d_s0 || !d_eps || !d_cost || !d_grad || (adam_t > 0 && (!d_m || !d_v)))
+    return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  PilcoArgs a = p->a;
+  a.H = H;
+  a.reward = reward;
+  a.phi = d_phi;
+  a.phi_out = d_phi;
+  a.m = d_m;
+  a.v = d_v;
+  a.W = d_W;
+  a.s0 = d_s0;
+  a.eps = d_eps;
+  a.cost = d_cost;
+  a.grad = d_grad;
+  a.st = d_states ? d_states : p->st_own;
+  a.ac = d_actions ? d_actions : p->ac_own;
+
+  // the scalars of this call: not part of a captured graph
+  float lr_t = 0.0f;
+  if (adam_t > 0) lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(0.999, (double)adam_t)) / (1.0 - std::pow(0.9, (double)adam_t)));
+  auto tiles = [](const PilcoNet &net) {
+    int n = 0;
+    for (int l = 0; l < net.L; ++l) n += cdiv(net.dims[l], 32) * cdiv(net.dims[l + 1], 32);
+    return n;
+  };
+  PYZ_LAUNCH(k_pilco_set, dim3(std::max({tiles(a.pol), tiles(a.dyn), cdiv(H + 1, 256)}), a.K + 2), dim3(256), 0, st, a, p->ctl,
+             freq, (double)gamma, lr_t, adam_t > 0 ? 1 : 0);
+  PYZ_LAUNCH_CHECK();
+
+  const size_t lds_f = pilco_fwd_lds(a.K, a.S, a.maxw), lds_b = pilco_bwd_lds(a.K, a.S, a.maxw, a.pw);
+  auto chain = [&]() {
+    PilcoArgs g = a;
+    for (int t = 1; t <= H; ++t) {
+      g.t = t;
+      PYZ_LAUNCH(k_pilco_fwd, dim3(a.K), dim3(PILCO_THREADS), lds_f, st, g);
+    }
+    g.t = H + 1;
+    PYZ_LAUNCH(k_pilco_tail, dim3(a.K), dim3(PILCO_THREADS), lds_f, st, g);
+    for (int t = H; t >= 1; --t) {
+      g.t = t;
+      PYZ_LAUNCH(k_pilco_bwd, dim3(a.K), dim3(PILCO_THREADS), lds_b, st, g);
+    }
+    PYZ_LAUNCH(k_pilco_close, dim3(cdiv(a.Dp, 256)), dim3(256), 0, st, g);
+    PYZ_LAUNCH_CHECK();
+    return PYZ_OK;
+  };
+  if (!use_graph || st == nullptr || pyz_probe().on) return chain();   // (the legacy default stream cannot be captured)
+  unsigned long long key = 1469598103934665603ull;
+  auto mix = [&](unsigned long long v) { key = (key ^ v) * 1099511628211ull; };
+  for (const void *q : {(const void *)d_phi, (const void *)d_m, (const void *)d_v, (const void *)d_W, (const void *)d_s0,
+                        (const void *)d_eps, (const void *)d_cost, (const void *)d_grad, (const void *)a.st, (const void *)a.ac})
+    mix((unsigned long long)(uintptr_t)q);
+  mix((unsigned long long)reward);
+  p->graphs.rekey(key);
+  p->graphs.begin_call();
+  return p->graphs.launch(H, (unsigned long long)freq, 0, 4, st, chain);
 }
 
 // ---------------------------------------------------------------- measurement hook

@@ -656,6 +656,102 @@ class MLPPlan:
         return xgrad, xadv, losses
 
 
+class PilcoPlan:
+    """Owns one `pyz_pilco` handle: the policy update of Deep-PILCO (dynamics/deep_pilco.py:247-326) for a policy net
+    `policy_spec` (dims (S, hidden..., A)) and `particles` draws of a dynamics net `dynamics_spec` (dims (S + A, hidden...,
+    S), last layer linear), with the tape of up to max_horizon steps.  The specs' `loss` is not used.  cost and grad live
+    in buffers of the plan (so do states and actions unless the caller passes its own): a captured graph is replayed
+    while the caller's tensors stay where they are, and the returned tensors are overwritten by the next call."""
+
+    def __init__(self, policy_spec: MLPSpec, dynamics_spec: MLPSpec, particles: int, max_horizon: int, device=None):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError("bayesian_inference_for_nn_amd needs an MI355X (no HIP device visible); there is no CPU path")
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.policy_spec, self.dynamics_spec = policy_spec, dynamics_spec
+        self.K, self.max_horizon = int(particles), int(max_horizon)
+        self.S, self.A = int(policy_spec.dims[0]), int(policy_spec.dims[-1])
+        self.D_pol, self.D_dyn = policy_spec.n_params, dynamics_spec.n_params
+        pd = (C.c_int32 * len(policy_spec.dims))(*policy_spec.dims)
+        pa = (C.c_int32 * len(policy_spec.acts))(*[ACT[a] for a in policy_spec.acts])
+        dd = (C.c_int32 * len(dynamics_spec.dims))(*dynamics_spec.dims)
+        da = (C.c_int32 * len(dynamics_spec.acts))(*[ACT[a] for a in dynamics_spec.acts])
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.pyz_pilco_create(policy_spec.n_layers, pd, pa, dynamics_spec.n_layers, dd, da, self.K,
+                                            self.max_horizon, C.byref(h)))
+        self.h = h
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._cost, self._grad = torch.zeros(1, **f32), torch.zeros(self.D_pol, **f32)
+        self._states = torch.zeros((self.max_horizon + 1, self.K, self.S), **f32)
+        self._actions = torch.zeros((self.max_horizon, self.K, self.A), **f32)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.pyz_pilco_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(self.lib.pyz_pilco_workspace_bytes(self.h))
+
+    @staticmethod
+    def default_freq(horizon: int) -> int:
+        """deep_pilco.py:280: every freq-th step's reward is counted."""
+        return max(int(int(horizon) / 25), 1)
+
+    def _steps(self, t, rows, inner, name):
+        """A (>= rows, *inner) float32 buffer of per-step blocks: the kernels use its first `rows` blocks."""
+        _f32(t, name=name)
+        if t.dim() != 1 + len(inner) or tuple(t.shape[1:]) != tuple(inner) or t.shape[0] < rows:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected (>= {rows}, {', '.join(str(v) for v in inner)})")
+        return t
+
+    def policy_step(self, phi, m, v, t, W, s0, eps, horizon, gamma, reward, lr=1e-3, freq=None, use_graph=True, states=None,
+                    actions=None):
+        """One rollout of `horizon` steps from s0 (K, S) under the dynamics draws W (K, D_dyn) with the unit normals
+        eps (>= horizon, K, S), its cost and gradient, and the t-th Keras-Adam update of phi (D_pol,) with moments
+        m, v (in place; t >= 1).  reward: a name of dynamics.all_rewards.  Returns (cost (1,), grad (D_pol,))."""
+        return self._call(phi, m, v, int(t), W, s0, eps, horizon, gamma, reward, lr, freq, use_graph, states, actions)[:2]
+
+    def rollout_grad(self, phi, W, s0, eps, horizon, gamma, reward, freq=None, use_graph=True, states=None, actions=None):
+        """(cost (1,), grad (D_pol,), states (horizon + 1, K, S), actions (horizon, K, A)) of one rollout; phi is not
+        changed.  states / actions: optional buffers of at least that many steps to write into."""
+        return self._call(phi, None, None, 0, W, s0, eps, horizon, gamma, reward, 0.0, freq, use_graph, states, actions)
+
+    def _call(self, phi, m, v, t, W, s0, eps, horizon, gamma, reward, lr, freq, use_graph, states, actions):
+        H = int(horizon)
+        if not 1 <= H <= self.max_horizon:
+            raise ValueError(f"horizon {H} outside [1, {self.max_horizon}]")
+        freq = self.default_freq(H) if freq is None else int(freq)
+        if freq < 1:
+            raise ValueError("freq must be >= 1")
+        if reward not in _lib.REWARD:
+            raise ValueError(f"unknown reward {reward!r}: one of {sorted(_lib.REWARD)}")
+        if t < 0:
+            raise ValueError("t must be >= 0")
+        _f32(phi, (self.D_pol,), "phi")
+        if t > 0:
+            _f32(m, (self.D_pol,), "m")
+            _f32(v, (self.D_pol,), "v")
+        _f32(W, (self.K, self.D_dyn), "W")
+        _f32(s0, (self.K, self.S), "s0")
+        self._steps(eps, H, (self.K, self.S), "eps")
+        states = self._states if states is None else self._steps(states, H + 1, (self.K, self.S), "states")
+        actions = self._actions if actions is None else self._steps(actions, H, (self.K, self.A), "actions")
+        check(self.lib.pyz_pilco_policy_step(self.h, ptr(phi), ptr(m) if t > 0 else None, ptr(v) if t > 0 else None, t,
+                                             ptr(W), ptr(s0), ptr(eps), H, freq, float(gamma), _lib.REWARD[reward], float(lr),
+                                             ptr(self._cost), ptr(self._grad), ptr(states), ptr(actions),
+                                             1 if use_graph else 0, _stream()))
+        return self._cost, self._grad, states[:H + 1], actions[:H]
+
+
 class KernelProbe:
     """with KernelProbe(max_launches) as kp: ...launch steps...  -> kp.launches = [(kernel expression, microseconds)]
     in launch order: each kernel's own begin / end timestamps (measurement only; runs launch eagerly inside)."""

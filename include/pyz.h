@@ -510,6 +510,43 @@ int pyz_corrupt_rows(const float *d_x, int64_t n, int h, int w, int ch, int kind
  *     workgroup added in workgroup order (no floating-point atomics: the same bits on every call). */
 int pyz_score_rows(const float *d_mean, int groups, int64_t n, int C, const void *d_y, int kind, void *d_out, void *stream);
 
+/* ---- D1: one policy update of Deep-PILCO (Pyesian/dynamics/deep_pilco.py:247-326): a rollout of K particles through
+ * the policy and K draws of a dynamics network, its cost, the cost's gradient with respect to the policy's parameters
+ * and, when asked, one Keras-Adam update of them.  Both networks are Dense stacks in the flat parameter order:
+ * policy dims (S, hidden..., A), dynamics dims (S + A, hidden..., S).  Hidden activations: linear / relu / tanh / sigmoid;
+ * the policy's last layer may also be softmax; the dynamics' last layer must be linear.
+ *   for t = 1..H, s = s_{t-1}:  a_i = policy(phi, s_i)  (the output itself: softmax probabilities, never an arg-max)
+ *                               y_i = dynamics(W_i, [s_i, a_i])
+ *                               m = mean_i y_i,  sd = sqrt(mean_i (y_i - m)^2),  s_t,i = m + sd * eps[t-1][i]
+ *   cost = -mean_i r(s_0,i, 0) - sum over t in 1..H with t % freq == 0 of gamma^(t / freq) * mean_i r(s_t,i, t)
+ * Rewards (dynamics/custom.py:6-18):
+ *   PYZ_REWARD_CART  r = -s2 - s3 s2 + t (-s2^2 + 0.2095^2)              S >= 4
+ *   PYZ_REWARD_ACB   r = 4 - 3 s0 - (s0 s2 - s1 s3) + s4^2              S >= 5
+ * pyz_pilco_create refuses (PYZ_E_INVALID, no device touched) K < 2 (sd is identically 0 and the gradient NaN), a
+ * dynamics net whose last layer is not linear or whose dims do not fit the policy's, and anything past the limits
+ * K <= 256, S + A <= 64, layer widths <= 512, at most 8 Dense layers per net, max_horizon <= 4096.  The handle owns the
+ * tape of max_horizon steps (pyz_pilco_workspace_bytes).
+ * pyz_pilco_policy_step: d_phi float32[D_pol]; d_W (K, D_dyn); d_s0 (K, S); d_eps (H, K, S) unit normals (the kernels draw
+ * nothing: fill it with pyz_fill_normal, stream PYZ_STREAM_PILCO = 8 of csrc/pyz_rng.h); gamma the discount.  adam_t = 0: gradient only, d_phi
+ * is not written and d_m / d_v may be NULL.  adam_t >= 1: m += (g - m)(1 - 0.9); v += (g^2 - v)(1 - 0.999);
+ * phi -= lr sqrt(1 - 0.999^t) / (1 - 0.9^t) * m / (sqrt(v) + 1e-7).  Outputs: d_cost float32[1], d_grad float32[D_pol],
+ * optional d_states (H + 1, K, S) and d_actions (H, K, A).  2 H + 3 launches; every sum runs in one fixed order, so the
+ * bits are the same on every call.  use_graph != 0: the 2 H + 2 launches behind the first are captured once per (H, freq,
+ * reward and every pointer argument) as one chain on `stream` and replayed.  PYZ_E_INVALID for a reward whose indices
+ * exceed S or an unknown one, freq < 1, a null pointer; PYZ_E_SHAPE for H outside [1, max_horizon].  Nothing is launched
+ * after a refusal. */
+#define PYZ_REWARD_CART 0
+#define PYZ_REWARD_ACB 1
+typedef struct pyz_pilco pyz_pilco;
+int pyz_pilco_create(int n_policy_layers, const int32_t *h_policy_dims, const int32_t *h_policy_acts, int n_dynamics_layers,
+                     const int32_t *h_dynamics_dims, const int32_t *h_dynamics_acts, int particles, int max_horizon,
+                     pyz_pilco **out);
+int pyz_pilco_destroy(pyz_pilco *plan);
+int64_t pyz_pilco_workspace_bytes(const pyz_pilco *plan);
+int pyz_pilco_policy_step(pyz_pilco *plan, float *d_phi, float *d_m, float *d_v, int64_t adam_t, const float *d_W,
+                          const float *d_s0, const float *d_eps, int H, int freq, float gamma, int reward, float lr,
+                          float *d_cost, float *d_grad, float *d_states, float *d_actions, int use_graph, void *stream);
+
 /* ---- noise: d_out[i] = mean + std * z_i, z from Philox stream (seed, stream, step).
  * (tf.random.normal at SGLD.py:67, HMC.py:171; tfp samplers at BBB.py:234-237,
  * SVGD.py:154, distributions/tf/TensorflowProbabilityDistribution.py:55-58.) */
