@@ -15,6 +15,8 @@ GAMMA_MEDIAN = -1.0       # PYZ_SVGD_GAMMA_MEDIAN
 
 STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM, STREAM_BSAM, STREAM_CORRUPT = 0, 1, 2, 3, 4, 5, 6, 7
 STREAM_PILCO = 8           # PYZ_STREAM_PILCO
+STREAM_FSVI = 9            # PYZ_STREAM_FSVI (csrc/pyz_rng.h)
+FSVI_MAX_N, FSVI_MAX_D = 1024, 2048    # PYZ_FSVI_MAX_N / PYZ_FSVI_MAX_D
 REWARD = {"Cart": 0, "Acb 2 factors": 1}    # PYZ_REWARD_*; the names of dynamics.all_rewards
 
 
@@ -78,6 +80,10 @@ SIGNATURES = {
     "pyz_svgd_gram_groups": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
     "pyz_svgd_kernel_matrix_groups": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _f, _p]),
     "pyz_svgd_combine": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, C.c_int, _p, _p, _f, _f, _i64, _p, _p]),
+    "pyz_fsvi_check": (C.c_int, [C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pyz_fsvi_step": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, _p, _p, C.c_int, C.c_int, _p, _p, _f, _i64, _u64, _p, _p, _p,
+                                _p, _p, _p, _p, _p, _p, _p]),
+    "pyz_spd_solve_f64": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, _p]),
     "pyz_predict": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
     "pyz_predict_moments": (C.c_int, [_p, _p, C.c_int, _p, C.c_int, _p, _p, _p]),
     "pyz_grid_rows": (C.c_int, [_p, C.c_int, _f, _f, C.c_int, _f, _f, C.c_int, _i64, _i64, _p, _p]),

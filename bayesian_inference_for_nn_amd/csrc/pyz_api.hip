@@ -8,6 +8,7 @@
 
 #include "pyz_common.h"
 #include "pyz_corrupt.h"
+#include "pyz_fsvi.h"
 #include "pyz_fused.h"
 #include "pyz_gemm.h"
 #include "pyz_gemm_ring.h"
@@ -84,6 +85,8 @@ struct Extra {  // lazily sized buffers kept beside the plan
   unsigned long long hr_count = 0;
   // slot 0 = a chunk of proposals, the others = remainders by exact length (LRU); its captures: those of the last pyz_hmc_run
   PyzGraphCache<PYZ_GRAPH_CHUNKS> hmc_run_graphs;
+  void *fsvi_buf = nullptr;      // pyz_fsvi_step: Xp, the two float64 systems, their right-hand sides, flags and loss partials
+  size_t fsvi_cap = 0;
 };
 
 }  // namespace
@@ -778,7 +781,7 @@ int pyz_mlp_destroy(pyz_mlp *mm) {
     if (m->act[l]) (void)hipFree(m->act[l]);
     if (m->delta[l]) (void)hipFree(m->delta[l]);
   }
-  void *ptrs[] = {m->grad, m->grad2, m->qsave, m->part, m->x.part2, m->scal, m->ctl, m->tab_bs, m->xb, m->x.hm_buf, m->x.hm_res_buf, m->x.gs_res_buf, m->x.fwd_part, m->nonfinite, m->x.hr_buf, m->x.hr_tab, m->x.tab_bc};
+  void *ptrs[] = {m->grad, m->grad2, m->qsave, m->part, m->x.part2, m->scal, m->ctl, m->tab_bs, m->xb, m->x.hm_buf, m->x.hm_res_buf, m->x.gs_res_buf, m->x.fwd_part, m->nonfinite, m->x.hr_buf, m->x.hr_tab, m->x.tab_bc, m->x.fsvi_buf};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (m->x.tab_host) {
@@ -962,6 +965,182 @@ int pyz_bsam_step(pyz_mlp *m, float *d_theta, float *d_m, float *d_v, const floa
     PYZ_LAUNCH(k_bsam_update, grid, block, 0, st, d_theta, d_m, d_v, m->grad, m->grad2, m->D, a.a, m->ctl, m->part,
                m->cur_nblk, d_loss + 1, m->nonfinite);
   }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- FSVI (FSVI.py:60-147, DESIGN A8)
+// what FSVI can run on, from the shape alone (no device is touched): FSVI.py:160-163 squeezes f[:, 0], :95 calls the loss
+// with swapped arguments, and the D x D Stein system of :187-195 is dense
+int pyz_fsvi_check(int n_layers, const int32_t *h_dims, const int32_t *h_acts, int loss, int k, int batch, int batch_size) {
+  if (!h_dims || !h_acts) return pyz_fail(PYZ_E_INVALID, "null argument");
+  if (n_layers < 1 || n_layers > PYZ_MAX_LAYERS) return pyz_fail(PYZ_E_INVALID, "n_layers %d outside [1, %d]", n_layers, PYZ_MAX_LAYERS);
+  if (loss != PYZ_LOSS_MSE) return pyz_fail(PYZ_E_INVALID, "FSVI needs the MeanSquaredError loss (FSVI.py:95 swaps the loss's arguments)");
+  if (h_acts[n_layers - 1] == PYZ_ACT_SOFTMAX) return pyz_fail(PYZ_E_INVALID, "FSVI does not take a softmax last layer");
+  if (h_dims[n_layers] != 1)
+    return pyz_fail(PYZ_E_INVALID, "FSVI needs a last layer of exactly one unit, not %d (FSVI.py:160 squeezes f[:, 0])", h_dims[n_layers]);
+  if (k < 1) return pyz_fail(PYZ_E_INVALID, "FSVI needs k >= 1 particles, not %d", k);
+  if (batch < 1 || batch_size < 1 || batch > batch_size)
+    return pyz_fail(PYZ_E_INVALID, "batch %d outside [1, batch_size = %d]", batch, batch_size);
+  if ((long long)batch + batch_size > PYZ_FSVI_MAX_N)
+    return pyz_fail(PYZ_E_INVALID, "batch + measurement rows n = %lld exceed the limit of %d", (long long)batch + batch_size, PYZ_FSVI_MAX_N);
+  long long D = 0;
+  for (int l = 0; l < n_layers; ++l) {
+    if (h_dims[l] < 1) return pyz_fail(PYZ_E_INVALID, "dims[%d] = %d", l, h_dims[l]);
+    D += (long long)(h_dims[l] + 1) * h_dims[l + 1];
+  }
+  if (D > PYZ_FSVI_MAX_D)
+    return pyz_fail(PYZ_E_INVALID, "D = %lld weights exceed the limit of %d (the Stein system is D x D float64 per particle)", D, PYZ_FSVI_MAX_D);
+  return PYZ_OK;
+}
+
+int pyz_spd_solve_f64(double *d_a, double *d_rhs, int n, int n_systems, int *d_fail, void *stream) {
+  if (!d_a || !d_rhs) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (n < 1 || n > PYZ_SPD_MAX_N) return pyz_fail(PYZ_E_INVALID, "system size %d outside [1, %d]", n, PYZ_SPD_MAX_N);
+  if (n_systems < 1 || n_systems > 65535) return pyz_fail(PYZ_E_INVALID, "system count %d outside [1, 65535]", n_systems);
+  int rc;
+  if ((rc = pyz_spd_prepare())) return rc;
+  pyz_launch_spd(d_a, d_rhs, n, n_systems, d_fail, as_stream(stream));
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_fsvi_step(pyz_mlp *m, float *d_mu, float *d_particles, int k, float *d_adam_m, float *d_adam_v, const float *d_x,
+                  const float *d_y, const int32_t *d_row_idx, int batch, int batch_size, const float *d_lo, const float *d_hi,
+                  float lr, int64_t t, uint64_t seed, const float *d_xm, const float *d_noise, const float *d_eps,
+                  double *d_alpha, float *d_stein, float *d_grad, float *d_xp, float *d_f, float *d_loss, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  int rc;
+  if ((rc = pyz_fsvi_check(m->L, m->dims, m->acts, m->loss, k, batch, batch_size))) return rc;
+  const int n = batch + batch_size, F = m->dims[0];
+  if ((rc = check_call(m, k, n))) return rc;   // the plan's rows hold batch + measurement rows
+  if (!d_mu || !d_particles || !d_adam_m || !d_adam_v || !d_x || !d_y || !d_loss || (!d_xm && (!d_lo || !d_hi)))
+    return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (t < 1 || t >= (1LL << 29)) return pyz_fail(PYZ_E_INVALID, "step t = %lld outside [1, 2^29)", (long long)t);
+  const long long D = m->D;
+  // workspace: allocated on the first call, grown when a call needs more, owned by the plan
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t o_xp = 0, o_gram = o_xp + up(sizeof(float) * (size_t)k * n * F),
+               o_alpha = o_gram + up(sizeof(double) * (size_t)k * n * n), o_skm = o_alpha + up(sizeof(double) * (size_t)k * n),
+               o_srhs = o_skm + up(sizeof(double) * (size_t)k * D * D), o_loss = o_srhs + up(sizeof(double) * (size_t)k * D),
+               o_fail = o_loss + up(sizeof(double) * (size_t)k), total = o_fail + up(sizeof(int) * (size_t)2 * k);
+  if ((rc = ensure_bytes(&full(m)->x.fsvi_buf, &full(m)->x.fsvi_cap, total, m))) return rc;
+  if ((rc = need_grad(m, k))) return rc;
+  if ((rc = pyz_spd_prepare())) return rc;
+  unsigned char *ws = static_cast<unsigned char *>(full(m)->x.fsvi_buf);
+  float *xp = d_xp ? d_xp : reinterpret_cast<float *>(ws + o_xp);
+  double *gram = reinterpret_cast<double *>(ws + o_gram);
+  double *alpha = d_alpha ? d_alpha : reinterpret_cast<double *>(ws + o_alpha);
+  double *skm = reinterpret_cast<double *>(ws + o_skm), *srhs = reinterpret_cast<double *>(ws + o_srhs);
+  double *loss_part = reinterpret_cast<double *>(ws + o_loss);
+  int *fail = reinterpret_cast<int *>(ws + o_fail);
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, n, lr, t, 0, 0, st))) return rc;
+
+  FsviInputs in{};                                   // FSVI.py:86-89, 106, 197-212
+  in.x = d_x;
+  in.row_idx = d_row_idx;
+  in.lo = d_lo;
+  in.hi = d_hi;
+  in.xm = d_xm;
+  in.noise = d_noise;
+  in.xp = xp;
+  in.k = k;
+  in.b = batch;
+  in.B = batch_size;
+  in.F = F;
+  in.seed = seed;
+  in.t4 = (uint32_t)(4 * t);
+  PYZ_LAUNCH(k_fsvi_inputs, dim3(cdiv((long long)k * n * F, 256)), dim3(256), 0, st, in);
+
+  // the Stein system needs the particles only (FSVI.py:114)
+  PYZ_LAUNCH(k_fsvi_stein_system, dim3((unsigned)D, k), dim3(256), 0, st, d_particles, (int)D, skm, srhs);
+  pyz_launch_spd(skm, srhs, (int)D, k, fail + k, st);
+
+  for (int l = 0; l < m->L; ++l) {                    // FSVI.py:108 (the forward of :91 gives the same batch rows)
+    DenseArgs g = forward_args(m, l, d_particles, D, xp, nullptr, m->ctl, nullptr);
+    if (l == 0) g.in_pstride = (long long)n * F;      // every particle has its own input rows
+    g.wt = pyz_wt_for(k);
+    pyz_launch_fwd(g, n, k, st);
+  }
+  const float *f = m->act[m->L - 1];
+  PYZ_LAUNCH(k_fsvi_gram, dim3(cdiv((long long)n * n, 256), k), dim3(256), 0, st, xp, n, F, f, (long long)m->max_batch, gram, alpha, d_f);
+  pyz_launch_spd(gram, alpha, n, k, fail, st);         // FSVI.py:160-163: d gp_ll / d f = -K^-1 f
+
+  FsviDelta dg{};                                    // FSVI.py:95-98, 111
+  const int l = m->L - 1;
+  dg.f = f;
+  dg.f_pstride = m->max_batch;
+  dg.y = d_y;
+  dg.row_idx = d_row_idx;
+  dg.alpha = alpha;
+  dg.delta_last = m->delta[l];
+  dg.loss_part = loss_part;
+  dg.H = m->dims[l];
+  if (l > 0) {
+    dg.h = m->act[l - 1];
+    dg.h_pstride = (long long)m->max_batch * dg.H;
+    dg.delta_prev = m->delta[l - 1];
+    dg.act_prev = m->acts[l - 1];
+  } else {
+    dg.h = xp;
+    dg.h_pstride = (long long)n * F;
+    dg.delta_prev = nullptr;
+  }
+  dg.theta = d_particles;
+  dg.grad = m->grad;
+  dg.D = D;
+  dg.w_off = m->w_off[l];
+  dg.b = batch;
+  dg.n = n;
+  dg.act_last = m->acts[l];
+  dg.cdat = (float)((double)k / (double)batch_size * 2.0 / (double)batch);   // FSVI.py:98: k / B with the hyperparameter B
+  dg.inv_k = 1.0 / (double)k;
+  PYZ_LAUNCH(k_fsvi_delta, dim3(k), dim3(256), 0, st, dg);
+
+  launch_bwd_data_hidden(m, d_particles, D, k, n, m->ctl, st);   // delta[L-3 .. 0]
+  for (int ll = m->L - 2; ll >= 0; --ll) {              // [dW; db] of the layers below the last
+    DenseArgs g{};
+    g.K = m->dims[ll];
+    g.N = m->dims[ll + 1];
+    if (ll == 0) {
+      g.in = xp;
+      g.in_pstride = (long long)n * F;
+    } else {
+      g.in = m->act[ll - 1];
+      g.in_pstride = (long long)m->max_batch * g.K;
+    }
+    g.lda = g.K;
+    g.aux = m->delta[ll];
+    g.aux_pstride = (long long)m->max_batch * g.N;
+    g.out = m->grad;
+    g.out_pstride = D;
+    g.w_off = m->w_off[ll];
+    g.ctl = m->ctl;
+    pyz_launch_bwd_weight(g, n, k, st);
+  }
+
+  FsviUpdate u{};                                    // FSVI.py:115-138, 228-231
+  u.mu = d_mu;
+  u.adam_m = d_adam_m;
+  u.adam_v = d_adam_v;
+  u.particles = d_particles;
+  u.grad = m->grad;
+  u.stein_sol = srhs;
+  u.eps = d_eps;
+  u.stein_out = d_stein;
+  u.grad_out = d_grad;
+  u.loss_part = loss_part;
+  u.fail = fail;
+  u.loss = d_loss;
+  u.nonfinite = m->nonfinite;
+  u.D = D;
+  u.k = k;
+  u.inv_k = (float)(1.0 / (double)k);
+  u.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(0.999, (double)t)) / (1.0 - std::pow(0.9, (double)t)));
+  u.seed = seed;
+  u.t4 = (uint32_t)(4 * t);
+  PYZ_LAUNCH(k_fsvi_update, dim3(cdiv(D, 256)), dim3(256), 0, st, u);
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
 }

@@ -21,6 +21,7 @@
 #define PYZ_STREAM_BSAM 6u   // BSAM weight perturbation (BSAM.py:63-68), step = the optimizer step
 #define PYZ_STREAM_CORRUPT 7u  // noise of the image corruptions (visualisations/Robustness.py:10-38), step = 8 * kind + severity; see below
 #define PYZ_STREAM_PILCO 8u    // the unit normals of a Deep-PILCO rollout (dynamics/deep_pilco.py:257-261), step = the policy update
+#define PYZ_STREAM_FSVI 9u     // FSVI (FSVI.py:87,205,231): step 4t the uniforms of X_M, 4t + 1 the input noise z_i, 4t + 2 the redraw; step 0 the initial particles
 // PYZ_STREAM_PREDICT, one draw (step) of a distribution over len elements:
 //   k_sample_normal_rows    z(e)  = element e, e < len
 //   k_sample_lowrank_rows   z1(e) = element e, e < len;  z2(c) = element 4 * ceil(len / 4) + c, c < k

@@ -575,6 +575,56 @@ class MLPPlan:
         check(self.lib.pyz_svgd_combine(self.h, ptr(particles), n_local, ptr(all_particles), n_total, int(row0), ptr(adam_m),
                                         ptr(adam_v), float(lr), _gamma(gamma), int(t), ptr(loss_out), _stream()))
 
+    # ------------------------------------------------------------------ F1
+    def fsvi_step(self, mu, particles, adam_m, adam_v, x, y, batch_size, lr, t, seed, loss_out, lo=None, hi=None, xm=None,
+                  noise=None, eps=None, want_terms=False, batch=None, row_idx=None):
+        """FSVI.step (FSVI.py:60-147, DESIGN A8): one step of mu (D,), its Adam slots and the k rows of particles (k, D) on
+        the `batch` rows of x picked by row_idx plus batch_size measurement rows; the plan needs max_batch >= batch +
+        batch_size and max_particles >= k.  Draws come from the Philox stream (seed, STREAM_FSVI, 4 t ..) unless injected:
+        xm (batch_size, F), noise (k, F), eps (k, D); lo / hi (F,) bound the measurement set when xm is None.  loss_out:
+        (1,) float32.  want_terms: returns dict(alpha (k, n) float64, stein (k, D), grad (D,), xp (k, n, F), f (k, n))."""
+        k = int(particles.shape[0]) if particles.dim() == 2 else 0
+        F, B = self.spec.dims[0], int(batch_size)
+        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+        dims = (C.c_int32 * len(self.spec.dims))(*self.spec.dims)
+        acts = (C.c_int32 * len(self.spec.acts))(*[ACT[a] for a in self.spec.acts])
+        check(self.lib.pyz_fsvi_check(self.spec.n_layers, dims, acts, LOSS[self.spec.loss], k, batch, B))
+        n = batch + B
+        if n > self.max_batch or k > self.max_particles:
+            raise ValueError(f"the plan holds {self.max_batch} rows x {self.max_particles} particles; FSVI needs "
+                             f"batch + batch_size = {n} rows x {k}")
+        _f32(mu, (self.D,), "mu")
+        _f32(particles, (k, self.D), "particles")
+        _f32(adam_m, (self.D,), "adam_m")
+        _f32(adam_v, (self.D,), "adam_v")
+        _f32(loss_out, (1,), "loss_out")
+        self._check_xy(x, y, row_idx, batch)
+        if row_idx is not None and row_idx.numel() < batch:
+            raise ValueError("row_idx holds fewer than `batch` entries")
+        for t_, shape, nm in ((xm, (B, F), "xm"), (noise, (k, F), "noise"), (eps, (k, self.D), "eps"), (lo, (F,), "lo"),
+                              (hi, (F,), "hi")):
+            if t_ is not None:
+                _f32(t_, shape, nm)
+        if xm is None and (lo is None or hi is None):
+            raise ValueError("lo and hi are needed when xm is not given")
+        terms = None
+        if want_terms:
+            terms = dict(alpha=torch.empty((k, n), dtype=torch.float64, device=self.device),
+                         stein=torch.empty((k, self.D), dtype=torch.float32, device=self.device),
+                         grad=torch.empty((self.D,), dtype=torch.float32, device=self.device),
+                         xp=torch.empty((k, n, F), dtype=torch.float32, device=self.device),
+                         f=torch.empty((k, n), dtype=torch.float32, device=self.device))
+        g = terms or {}
+        check(self.lib.pyz_fsvi_step(self.h, ptr(mu), ptr(particles), k, ptr(adam_m), ptr(adam_v), ptr(x), ptr(y),
+                                     ptr(row_idx), batch, B, ptr(lo), ptr(hi), float(lr), int(t), int(seed), ptr(xm),
+                                     ptr(noise), ptr(eps), ptr(g.get("alpha")), ptr(g.get("stein")), ptr(g.get("grad")),
+                                     ptr(g.get("xp")), ptr(g.get("f")), ptr(loss_out), _stream()))
+        return terms
+
+    @property
+    def workspace_bytes(self) -> int:
+        return int(self.lib.pyz_mlp_workspace_bytes(self.h))
+
     # ------------------------------------------------------------------ R1
     def predict(self, weights, x, want_samples=True):
         _f32(weights, name="weights")
@@ -782,6 +832,20 @@ class KernelProbe:
             c, t = acc.get(name, (0, 0.0))
             acc[name] = (c + 1, t + v)
         return {k: (c, t / c) for k, (c, t) in acc.items()}
+
+
+def spd_solve(a: torch.Tensor, rhs: torch.Tensor):
+    """Solves the symmetric positive-definite float64 systems a (systems, n, n) x = rhs (systems, n) on the device
+    (pyz_spd_solve_f64: one workgroup per system, Cholesky + two substitutions).  rhs receives the solutions, a is scratch
+    afterwards.  Returns the int32 (systems,) flags: 1 where a pivot was not positive (that solution is NaN)."""
+    for t, nm in ((a, "a"), (rhs, "rhs")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise TypeError(f"{nm} must be a contiguous CUDA(HIP) float64 tensor")
+    if a.dim() != 3 or a.shape[1] != a.shape[2] or tuple(rhs.shape) != tuple(a.shape[:2]):
+        raise ValueError(f"a must be (systems, n, n) and rhs (systems, n), not {tuple(a.shape)} and {tuple(rhs.shape)}")
+    fail = torch.zeros((a.shape[0],), dtype=torch.int32, device=a.device)
+    check(_lib.load().pyz_spd_solve_f64(ptr(a), ptr(rhs), int(a.shape[1]), int(a.shape[0]), ptr(fail), _stream()))
+    return fail
 
 
 def fill_normal(out: torch.Tensor, seed: int, stream_id: int, step: int, mean: float = 0.0, std: float = 1.0):

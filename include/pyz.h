@@ -415,6 +415,42 @@ int pyz_svgd_gram_groups(pyz_mlp *mlp, const float *d_all, int n_total, int g_lo
 int pyz_svgd_kernel_matrix_groups(pyz_mlp *mlp, const double *d_groups, const float *d_all, int n_total, int row0,
                                   int n_local, float gamma, void *stream);
 
+/* ---- F1: FSVI.step (Pyesian/optimizers/FSVI.py:60-147; Rudner et al., "Tractable Function-Space Variational Inference in
+ * Bayesian Neural Networks"), as DESIGN assumption A8 defines it.  State: d_mu float32[D] with one Keras-legacy-Adam slot pair
+ * d_adam_m / d_adam_v (only optimizers[0] is used, :136), the k particles d_particles (k, D), the 1-based step t.
+ * With b = batch rows of this step (d_row_idx, or rows 0 .. b - 1 of d_x), B = batch_size, n = b + B, F inputs:
+ *   Xp_i (n, F): the batch rows + z_i, then X_M + (z_0 + ... + z_i), a sequential float32 sum (:86-89, 106), with
+ *     X_M[r][c] = lo[c] + u (hi[c] - lo[c]) (:197-212) and z_i = 0.1 N(0, 1) (:87);
+ *   f_i = model(W_i; Xp_i); ll_i = mean over the batch rows of (f_i - y)^2, its gradient scaled by k / B (:95-98);
+ *   alpha_i = (K_i + 1e-6 I)^-1 f_i with K_i[r][s] = exp(-|Xp_i[r] - Xp_i[s]|^2 / 2), float64 throughout (:149-165);
+ *   c2_i = -(K_w + 1e-3 I)^-1 rhs over the D weights of W_i as scalar points, float64, rounded once (:177-195);
+ *   g = sum_i [(k / B) grad ll_i - (1 / k) J_i^T alpha_i - (1 / k) c2_i], one backward pass per particle, fixed-order sums (:115-136);
+ *   Adam (beta_1 0.9, beta_2 0.999, epsilon 1e-7, step t) on d_mu, then W_i = mu + eps_i for every particle (:135-138, 228-231).
+ * d_loss[0] = sum_i ll_i / k (:123, 147).  Draws: Philox stream PYZ_STREAM_FSVI = 9 (csrc/pyz_rng.h) of `seed`, step 4 t for
+ * the uniforms of X_M (element r F + c), 4 t + 1 for the normals of z (element i F + c), 4 t + 2 for eps (element i D + e);
+ * or the caller's: d_xm (B, F), d_noise (k, F) (the z_i themselves), d_eps (k, D); NULL selects the stream.  d_lo / d_hi
+ * float32[F] are needed without d_xm.  Optional outputs (NULL: not written): d_alpha (k, n) float64, d_stein (k, D) the c2_i,
+ * d_grad float32[D] g, d_xp (k, n, F), d_f (k, n) the f_i.
+ * PYZ_E_INVALID, before anything is enqueued (pyz_fsvi_check is the same test on a bare shape, no device needed): a loss
+ * other than PYZ_LOSS_MSE, a last layer of other than one unit or with softmax, k < 1, batch outside [1, batch_size],
+ * n > 1024, D > 2048, t outside [1, 2^29), a null pointer.  PYZ_E_SHAPE: n > max_batch or k > max_particles of the plan.
+ * A pivot of either factorisation that is not positive makes d_loss NaN, counts in the plan's sentinel (pyz_check_finite)
+ * and leaves NaN in that particle's term; nothing is masked.  The workspace (the two float64 systems: k (n^2 + D^2) doubles)
+ * is allocated on the first call, owned by the plan and counted by pyz_mlp_workspace_bytes. */
+int pyz_fsvi_check(int n_layers, const int32_t *h_dims, const int32_t *h_acts, int loss, int k, int batch, int batch_size);
+int pyz_fsvi_step(pyz_mlp *mlp, float *d_mu, float *d_particles, int k, float *d_adam_m, float *d_adam_v, const float *d_x,
+                  const float *d_y, const int32_t *d_row_idx, int batch, int batch_size, const float *d_lo,
+                  const float *d_hi, float lr, int64_t t, uint64_t seed, const float *d_xm, const float *d_noise,
+                  const float *d_eps, double *d_alpha, float *d_stein, float *d_grad, float *d_xp, float *d_f,
+                  float *d_loss, void *stream);
+
+/* Batched symmetric positive-definite solve in float64 (the primitive of both FSVI terms; needs no plan): n_systems systems
+ * d_a (n_systems, n, n) row-major (the lower triangle is read), d_rhs (n_systems, n).  One workgroup per system: in-place
+ * lower Cholesky, forward and back substitution; d_rhs receives the solutions, d_a is scratch afterwards.  n <= 128 runs
+ * inside LDS, larger systems in global memory.  d_fail (optional, int32[n_systems]): 1 where a pivot was not positive (that
+ * solution is NaN-filled), else 0 -- a normal return.  1 <= n <= 2048, 1 <= n_systems <= 65535, else PYZ_E_INVALID. */
+int pyz_spd_solve_f64(double *d_a, double *d_rhs, int n, int n_systems, int *d_fail, void *stream);
+
 /* ---- R1: BayesianModel.predict (BayesianModel.py:106-129): S weight draws
  * d_weights (S, D) -> d_samples (S, n, out) with NaN -> 0, d_mean (n, out). */
 int pyz_predict(pyz_mlp *mlp, const float *d_weights, int n_samples, const float *d_x, int n,
