@@ -12,6 +12,7 @@ ACT = {"linear": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "softmax": 4}
 LOSS = {"scce": 0, "mse": 1, "bce": 2}
 SWEEP = {"gauss_seidel": 0, "jacobi": 1}
 GAMMA_MEDIAN = -1.0       # PYZ_SVGD_GAMMA_MEDIAN
+MAX_LANES = 64            # PYZ_MAX_LANES
 
 STREAM_SGLD, STREAM_BBB, STREAM_HMC, STREAM_INIT, STREAM_PREDICT, STREAM_VADAM, STREAM_BSAM, STREAM_CORRUPT = 0, 1, 2, 3, 4, 5, 6, 7
 STREAM_PILCO = 8           # PYZ_STREAM_PILCO
@@ -52,6 +53,11 @@ SIGNATURES = {
     "pyz_sgld_chains_step": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, _p, C.c_int, _f, _i64, _u64, _p, _p, _p]),
     "pyz_sgld_chains_run": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _i64,
                                       _i64, _u64, _p, C.c_int, _p]),
+    "pyz_sgld_lanes_step": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, _p, C.c_int, C.POINTER(_f), _i64, _u64, C.c_int, _p, _p,
+                                      _p]),
+    "pyz_sgld_lanes_run": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _i64,
+                                     _i64, _u64, C.c_int, _p, _p]),
+    "pyz_lane_scores": (C.c_int, [_p, _p, C.c_int, _p, _p, C.c_int, _p, _p, _p]),
     "pyz_sgd_run": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _i64, _p, C.c_int, _p]),
     "pyz_swag_run": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int,
                                _i64, _i64, _p, C.c_int, _p]),

@@ -5,6 +5,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "pyz_common.h"
 #include "pyz_corrupt.h"
@@ -21,6 +22,7 @@
 #include "pyz_surface.h"
 #include "pyz_rng.h"
 #include "pyz_sgld_chains.h"
+#include "pyz_sgld_lanes.h"
 
 namespace {
 
@@ -1648,6 +1650,153 @@ int pyz_sgld_chains_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_m
                             row_stride, seed, nullptr, d_losses, st);
     ++m->run_eager_steps;
   }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// ---- SGLD lanes (pyz_sgld_lanes.h): the chains step with a learning rate per lane and the seed seed + c * seed_stride.
+// The gradient pass is launch_sgld_chains_step's; k_sgld_update_lanes stands where k_sgld_update_chains stands there.
+static int sgld_lanes_check(const pyz_mlp *m, const void *theta, const void *mean, const void *sq, int n_lanes,
+                            const void *x, const void *y, const void *h_lr, const void *losses, int64_t n, int seed_stride) {
+  if (n_lanes < 1) return pyz_fail(PYZ_E_INVALID, "n_lanes %d: at least one lane", n_lanes);
+  if (n < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
+  if (seed_stride != 0 && seed_stride != 1)
+    return pyz_fail(PYZ_E_INVALID, "seed_stride %d: 0 (one noise stream for every lane) or 1 (seed + lane)", seed_stride);
+  if (!theta || !mean || !sq || !x || !y || !h_lr || !losses) return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_lanes > m->max_p || n_lanes > PYZ_MAX_LANES)
+    return pyz_fail(PYZ_E_SHAPE, "n_lanes %d outside [1, %d] of the plan and the library", n_lanes, std::min(m->max_p, PYZ_MAX_LANES));
+  return check_loss_combo(m);
+}
+
+static void launch_sgld_lanes_step(pyz_mlp *m, float *theta, float *mean, float *sq, int P, const float *x, const void *y,
+                                   const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
+                                   const float *h_lr, uint64_t seed, int seed_stride, const float *unit_noise, float *loss,
+                                   hipStream_t st) {
+  const StepCtl *ctl = m->ctl + slot;
+  WgradArgs u{};
+  u.mode = PYZ_UPD_NONE;
+  u.grad = m->grad;
+  u.grad_pstride = m->D;
+  const bool fused = can_fuse(m);
+  if (fused) u.ploss = m->scal;
+  launch_loss_backward(m, theta, m->D, P, x, y, row_idx, grid_batch, ctl, true, u, st);
+  if (!fused) PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, ctl, m->scal, m->nonfinite);
+  SgldLanesArgs a{};
+  a.c.theta = theta;
+  a.c.mean = mean;
+  a.c.sq_mean = sq;
+  a.c.grad = m->grad;
+  a.c.D = m->D;
+  a.c.grad_pstride = m->D;
+  a.c.groups = (m->D + 3) / 4;
+  a.c.ctl = ctl;
+  a.c.next = chained ? m->ctl + (slot ^ 1) : nullptr;
+  a.c.tab_bs = m->tab_bs;
+  a.c.tab_lr = m->tab_lr;
+  a.c.row_stride = row_stride;
+  a.c.seed = seed;
+  a.c.unit_noise = unit_noise;
+  a.c.ploss = m->scal;
+  a.c.loss = loss;
+  a.c.loss_indexed = chained ? 1 : 0;
+  a.seed_stride = (unsigned)seed_stride;
+  for (int c = 0; c < P; ++c) a.rates.lr[c] = h_lr[c];
+  // the chains kernel's grid rule: the launch fills the chip once
+  const long long per_lane = std::max<long long>(1, 8LL * pyz_cu_count() / P);
+  const dim3 grid((unsigned)std::min<long long>(cdiv(a.c.groups, 256), per_lane), (unsigned)P);
+  PYZ_LAUNCH(k_sgld_update_lanes, grid, dim3(256), 0, st, a);
+}
+
+int pyz_sgld_lanes_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
+                        const void *d_y, const int32_t *d_row_idx, int batch, const float *h_lr, int64_t n, uint64_t seed,
+                        int seed_stride, const float *d_unit_noise, float *d_loss, void *stream) {
+  int rc = sgld_lanes_check(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, h_lr, d_loss, n, seed_stride);
+  if (rc) return rc;
+  if ((rc = check_call(m, n_lanes, batch))) return rc;
+  if ((rc = need_grad(m, n_lanes))) return rc;
+  hipStream_t st = as_stream(stream);
+  set_ctl_lazy(m, batch, h_lr[0], n);   // (the StepCtl's rate is lane 0's; the update reads the launch's own)
+  launch_sgld_lanes_step(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, batch, 0, false, 0, h_lr, seed,
+                         seed_stride, d_unit_noise, d_loss, st);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// As pyz_sgld_chains_run: every step enqueued for its own batch size, the scalars from the StepCtl ping-pong; the rates
+// of step s are row s of the host's (n_steps, n_lanes) table, in that step's launch.  The device's rate table gets lane
+// 0's column (nobody reads it: it keeps the StepCtl meaningful).
+int pyz_sgld_lanes_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
+                       const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
+                       int n_steps, int64_t n0, int64_t slot0, uint64_t seed, int seed_stride, float *d_losses,
+                       void *stream) {
+  int rc = sgld_lanes_check(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, h_lr, d_losses, n0, seed_stride);
+  if (rc) return rc;
+  if (!d_row_idx || !h_batch_sizes) return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
+  if ((rc = need_grad(m, n_lanes))) return rc;
+  hipStream_t st = as_stream(stream);
+  const long long row_stride = m->max_batch;
+  std::vector<float> lane0((size_t)n_steps);
+  for (int s = 0; s < n_steps; ++s) lane0[s] = h_lr[(size_t)s * n_lanes];
+  if ((rc = upload_run_tables(m, h_batch_sizes, lane0.data(), n_steps, n0, slot0, nullptr, d_x, d_row_idx, 0, st))) return rc;
+  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    launch_sgld_lanes_step(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true,
+                           row_stride, h_lr + (size_t)s * n_lanes, seed, seed_stride, nullptr, d_losses, st);
+    ++m->run_eager_steps;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// The loss sum (and wrong rows) of every lane over n rows: one particle-batched forward per chunk of max_particles lanes,
+// as pyz_predict, with the last layer left at its logits where the loss head starts from them (one sigmoid unit), and
+// k_lane_scores over m->act[L - 1].
+int pyz_lane_scores(pyz_mlp *m, const float *d_weights, int n_lanes, const float *d_x, const void *d_y, int n,
+                    double *d_loss_sum, int64_t *d_errors, void *stream) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_lanes < 1 || n < 1) return pyz_fail(PYZ_E_INVALID, "n_lanes and n must be positive");
+  if (!d_weights || !d_x || !d_y || !d_loss_sum) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (n > m->max_batch) return pyz_fail(PYZ_E_SHAPE, "n %d exceeds the plan's max_batch %d", n, m->max_batch);
+  int rc = check_loss_combo(m);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st))) return rc;
+  const int L = m->L, nblk = cdiv(n, 256), S_max = std::min(m->max_p, n_lanes);
+  // stream-ordered scratch, gone when the last chunk's kernel has read it: two partial rows and a ticket per lane of a chunk
+  const size_t words = (size_t)S_max * nblk;
+  unsigned long long *ws = nullptr;
+  PYZ_HIP(hipMallocAsync((void **)&ws, sizeof(unsigned long long) * (2 * words + (size_t)(S_max + 1) / 2), st));
+  LaneScoreArgs g{};
+  g.last = m->act[L - 1];
+  g.C = m->dims[L];
+  g.pstride = (long long)m->max_batch * g.C;
+  g.loss = m->loss;
+  g.n = n;
+  g.y = d_y;
+  g.part = ws;
+  g.epart = ws + words;
+  g.ticket = reinterpret_cast<unsigned *>(ws + 2 * words);
+  for (int s0 = 0; s0 < n_lanes; s0 += m->max_p) {
+    const int S = std::min(m->max_p, n_lanes - s0);
+    const float *w = d_weights + (long long)s0 * m->D;
+    launch_forward(m, w, m->D, S, d_x, nullptr, n, m->ctl, st, nullptr, L - 1);
+    {   // the last layer: launch_forward's launch, the activation left off where the head takes the logit
+      DenseArgs f = forward_args(m, L - 1, w, m->D, d_x, nullptr, m->ctl, nullptr);
+      if (m->loss == PYZ_LOSS_BCE) f.act = PYZ_ACT_LINEAR;
+      f.wt = pyz_wt_for(S);
+      if (!pyz_launch_fwd_ring(f, n, S, st)) {
+        if (!f.row_idx && !f.init_on && !f.gather_out) f.rows_cap = std::min(n, m->max_batch);
+        pyz_launch_fwd(f, n, S, st);
+      }
+    }
+    PYZ_HIP(hipMemsetAsync(g.ticket, 0, sizeof(unsigned) * (size_t)S, st));
+    g.loss_sum = d_loss_sum + s0;
+    g.errors = d_errors ? reinterpret_cast<long long *>(d_errors) + s0 : nullptr;
+    PYZ_LAUNCH(k_lane_scores, dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, st, g);
+  }
+  PYZ_HIP(hipFreeAsync(ws, st));
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
 }

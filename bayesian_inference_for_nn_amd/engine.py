@@ -279,6 +279,72 @@ class MLPPlan:
                                            lr, n_steps, int(n0), int(slot0), int(seed), ptr(losses_out),
                                            1 if use_graph else 0, _stream()))
 
+    def _lane_rates(self, lrs, shape):
+        """Host float32 rates of the lanes, C-contiguous, of the given shape ((P,) for a step, (n_steps, P) for a run)."""
+        lr = np.ascontiguousarray(np.asarray(lrs, dtype=np.float32))
+        if lr.shape != tuple(shape):
+            raise ValueError(f"lane rates have shape {lr.shape}, expected {tuple(shape)}")
+        return lr
+
+    def _check_lanes(self, theta, mean, sq_mean, seed_stride):
+        P = self._check_chains(theta, mean, sq_mean)
+        if P > _lib.MAX_LANES:
+            raise ValueError(f"at most {_lib.MAX_LANES} lanes per call")
+        if seed_stride not in (0, 1):
+            raise ValueError("seed_stride must be 0 (one noise stream for every lane) or 1 (seed + lane)")
+        return P
+
+    def sgld_lanes_step(self, theta, mean, sq_mean, x, y, lrs, n, seed, loss_out, seed_stride=0, batch=None, row_idx=None,
+                        unit_noise=None):
+        """sgld_chains_step with a rate per lane (lrs: P host floats) and the seed seed + c * seed_stride for lane c."""
+        P = self._check_lanes(theta, mean, sq_mean, seed_stride)
+        lr = self._lane_rates(lrs, (P,))
+        if unit_noise is not None:
+            _f32(unit_noise, (P, self.D), "unit_noise")
+        _f32(loss_out, (P,), "loss_out")
+        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+        self._check_xy(x, y, row_idx, batch)
+        check(self.lib.pyz_sgld_lanes_step(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx), batch,
+                                           lr.ctypes.data_as(C.POINTER(C.c_float)), int(n), int(seed), int(seed_stride),
+                                           ptr(unit_noise), ptr(loss_out), _stream()))
+
+    def sgld_lanes_run(self, theta, mean, sq_mean, x, y, row_idx, batch_sizes: Sequence[int], lrs, n0, seed, losses_out,
+                       seed_stride=0, slot0=0):
+        """n = len(batch_sizes) steps of sgld_lanes_step without host work in between (see sgld_chains_run); lrs: host
+        (n_steps, P) rates, row s for step s; losses_out: float32 (slots, P), step s writes row slot0 + s."""
+        P = self._check_lanes(theta, mean, sq_mean, seed_stride)
+        n_steps = len(batch_sizes)
+        if n_steps < 1:
+            raise ValueError("at least one step")
+        lr = self._lane_rates(lrs, (n_steps, P))
+        self._check_xy(x, y, row_idx, 1)
+        if slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch:
+            raise ValueError("row_idx must hold (slot0 + n_steps) * max_batch entries")
+        _f32(losses_out, name="losses_out")
+        if losses_out.numel() < (slot0 + n_steps) * P:
+            raise ValueError("losses_out must hold (slot0 + n_steps) * n_lanes entries")
+        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
+            raise ValueError("batch size outside the plan")
+        bs = (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes])
+        check(self.lib.pyz_sgld_lanes_run(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx), bs,
+                                          lr.ctypes.data_as(C.POINTER(C.c_float)), n_steps, int(n0), int(slot0), int(seed),
+                                          int(seed_stride), ptr(losses_out), _stream()))
+
+    def lane_scores(self, weights, x, y, want_errors=True):
+        """The score of every row of weights (n_lanes, D) on the rows of x / y (at most max_batch): (loss_sum float64
+        (n_lanes,), errors int64 (n_lanes,) or None) on the device -- the sum over the rows of the plan's per-row loss,
+        and the misclassified rows (0 for MSE).  More lanes than max_particles go through in chunks."""
+        _f32(weights, name="weights")
+        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
+            raise ValueError(f"weights must be (n_lanes, {self.D})")
+        n = int(x.shape[0])
+        self._check_xy(x, y, None, n)
+        S = int(weights.shape[0])
+        loss_sum = torch.empty((S,), dtype=torch.float64, device=self.device)
+        errors = torch.empty((S,), dtype=torch.int64, device=self.device) if want_errors else None
+        check(self.lib.pyz_lane_scores(self.h, ptr(weights), S, ptr(x), ptr(y), n, ptr(loss_sum), ptr(errors), _stream()))
+        return loss_sum, errors
+
     def sgd_run(self, theta, x, y, row_idx, batch_sizes, lrs, losses_out, use_graph=True, slot0=0):
         """n = len(batch_sizes) SGD steps without host work in between (see sgld_run for the table layout)."""
         n_steps = len(batch_sizes)

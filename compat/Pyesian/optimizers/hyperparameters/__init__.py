@@ -1,1 +1,2 @@
-from bayesian_inference_for_nn_amd.optimizers.hyperparameters import HyperParameters  # noqa: F401
+from bayesian_inference_for_nn_amd.optimizers.hyperparameters import (  # noqa: F401
+    Constant, GridOptimizer, HyperParameters, HyperparameterOptimizer, Integer, Number, Parameter, Real, SGLDGridObjective)

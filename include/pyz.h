@@ -192,6 +192,34 @@ int pyz_sgld_chains_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq
                         const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0, int64_t slot0,
                         uint64_t seed, float *d_losses /* (slots, n_chains) */, int use_graph, void *stream);
 
+/* ---- SGLD lanes: n_lanes chains that differ by their hyper-parameters (a grid search's points side by side).
+ * pyz_sgld_chains_step with a learning rate per lane, h_lr[c] (HOST floats: they ride in the launch), and the Philox seed
+ * seed + c * seed_stride: seed_stride = 1 is the chains step (equal rates: bit for bit), seed_stride = 0 gives every lane
+ * ONE noise stream, so that lanes with equal starts differ by their rates alone.  d_unit_noise (n_lanes, D) or NULL.
+ * PYZ_E_INVALID, with no device touched: a null plan, a null pointer among the required ones, n_lanes < 1, a negative
+ * count, seed_stride outside {0, 1}.  PYZ_E_SHAPE: n_lanes above the plan's max_particles or above PYZ_MAX_LANES. */
+#define PYZ_MAX_LANES 64
+int pyz_sgld_lanes_step(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
+                        const void *d_y, const int32_t *d_row_idx, int batch, const float *h_lr /* host, [n_lanes] */,
+                        int64_t n, uint64_t seed, int seed_stride, const float *d_unit_noise,
+                        float *d_loss /* [n_lanes] */, void *stream);
+
+/* pyz_sgld_chains_run over pyz_sgld_lanes_step: step s takes the rates h_lr[s * n_lanes ..] (host, (n_steps, n_lanes)
+ * row-major).  Every step is enqueued for its own batch size (no hipGraph: pyz_last_run_info reports eager steps), nothing
+ * synchronises inside the call, and the results equal n_steps calls of pyz_sgld_lanes_step bit for bit. */
+int pyz_sgld_lanes_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
+                       const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes,
+                       const float *h_lr /* host, (n_steps, n_lanes) */, int n_steps, int64_t n0, int64_t slot0,
+                       uint64_t seed, int seed_stride, float *d_losses /* (slots, n_lanes) */, void *stream);
+
+/* The score of every lane on n contiguous rows of d_x / d_y (d_y as for pyz_mlp_loss_grad): d_loss_sum[c] = the sum over the
+ * rows of the plan's per-row loss (the loss head's float32 expressions; summed in float64, one partial per workgroup, the
+ * partials added in workgroup order: the same call gives the same bits), d_errors[c] (may be NULL) = the rows whose first
+ * argmax differs from the label (SCCE), the rows with (p > 0.5) != (y > 0.5) (BCE), 0 (MSE).  d_weights (n_lanes, D); more
+ * lanes than max_particles go through in chunks.  n <= max_batch (PYZ_E_SHAPE); rows at or beyond n are never read. */
+int pyz_lane_scores(pyz_mlp *mlp, const float *d_weights, int n_lanes, const float *d_x, const void *d_y, int n,
+                    double *d_loss_sum /* [n_lanes] */, int64_t *d_errors /* [n_lanes] or NULL */, void *stream);
+
 /* Device-resident multi-step SGD (SGD.py:42-69 under the train loop of Optimizer.py:121-134): the
  * arguments of pyz_sgld_run without the moment vectors, count and seed; step s applies
  * theta <- theta - h_lr[s] * grad on its batch and writes the batch loss to d_losses[slot0+s].
