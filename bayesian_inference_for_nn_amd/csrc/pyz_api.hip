@@ -1562,21 +1562,37 @@ int pyz_sgld_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, co
 
 // ---- SGLD, P chains per launch (pyz_sgld_chains.h).  One step = the particle-batched gradient pass of pyz_svgd_gradients
 // (all chains on ONE batch, PYZ_UPD_NONE into the plan's (P, D) gradient buffer, per-particle losses in the plan's scalars)
-// and k_sgld_update_chains behind it.
-static int sgld_chains_check(const pyz_mlp *m, const void *theta, const void *mean, const void *sq, int n_chains,
-                             const void *x, const void *y, const void *losses, int64_t n) {
-  if (n_chains < 1) return pyz_fail(PYZ_E_INVALID, "n_chains %d: at least one chain", n_chains);
+// and k_sgld_update_chains behind it.  SGLD lanes (pyz_sgld_lanes.h) are the same step with a learning rate per lane and
+// the seed seed + c * seed_stride: k_sgld_update_lanes stands where k_sgld_update_chains stands, nothing else differs.
+// `lanes`: the P rows are lanes -- their host rates h_lr and seed_stride are checked as well, and at most PYZ_MAX_LANES go.
+static int sgld_rows_check(const pyz_mlp *m, bool lanes, const void *theta, const void *mean, const void *sq, int P,
+                           const void *x, const void *y, const void *h_lr, const void *losses, int64_t n, int seed_stride) {
+  const char *row = lanes ? "lane" : "chain";
+  if (P < 1) return pyz_fail(PYZ_E_INVALID, "n_%ss %d: at least one %s", row, P, row);
   if (n < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
-  if (!theta || !mean || !sq || !x || !y || !losses) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (lanes && seed_stride != 0 && seed_stride != 1)
+    return pyz_fail(PYZ_E_INVALID, "seed_stride %d: 0 (one noise stream for every lane) or 1 (seed + lane)", seed_stride);
+  if (!theta || !mean || !sq || !x || !y || (lanes && !h_lr) || !losses)
+    return pyz_fail(PYZ_E_INVALID, lanes ? "null pointer" : "null device pointer");
   if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
-  if (n_chains > m->max_p)
-    return pyz_fail(PYZ_E_SHAPE, "n_chains %d outside [1, %d] of the plan", n_chains, m->max_p);
+  const int most = lanes ? std::min(m->max_p, PYZ_MAX_LANES) : m->max_p;
+  if (P > most)
+    return pyz_fail(PYZ_E_SHAPE, "n_%ss %d outside [1, %d] of the plan%s", row, P, most, lanes ? " and the library" : "");
   return check_loss_combo(m);
 }
 
-static void launch_sgld_chains_step(pyz_mlp *m, float *theta, float *mean, float *sq, int P, const float *x, const void *y,
-                                    const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
-                                    uint64_t seed, const float *unit_noise, float *loss, hipStream_t st) {
+// the update's launch fills the chip once: 8 workgroups of 256 threads per CU over all P rows (see pyz_sgld_chains.h)
+static dim3 sgld_rows_grid(long long groups, int P) {
+  const long long per_row = std::max<long long>(1, 8LL * pyz_cu_count() / P);
+  return dim3((unsigned)std::min<long long>(cdiv(groups, 256), per_row), (unsigned)P);
+}
+
+// lane_lr: the P host rates of this step's lanes (k_sgld_update_lanes, seed + c * seed_stride), or nullptr for chains
+// (k_sgld_update_chains: ctl->lr, seed + c)
+static void launch_sgld_rows_step(pyz_mlp *m, float *theta, float *mean, float *sq, int P, const float *x, const void *y,
+                                  const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
+                                  uint64_t seed, const float *lane_lr, int seed_stride, const float *unit_noise, float *loss,
+                                  hipStream_t st) {
   const StepCtl *ctl = m->ctl + slot;
   WgradArgs u{};
   u.mode = PYZ_UPD_NONE;
@@ -1604,152 +1620,101 @@ static void launch_sgld_chains_step(pyz_mlp *m, float *theta, float *mean, float
   a.ploss = m->scal;
   a.loss = loss;
   a.loss_indexed = chained ? 1 : 0;
-  // the launch fills the chip once: 8 workgroups of 256 threads per CU over all chains (see pyz_sgld_chains.h)
-  const long long per_chain = std::max<long long>(1, 8LL * pyz_cu_count() / P);
-  const dim3 grid((unsigned)std::min<long long>(cdiv(a.groups, 256), per_chain), (unsigned)P);
-  PYZ_LAUNCH(k_sgld_update_chains, grid, dim3(256), 0, st, a);
+  const dim3 grid = sgld_rows_grid(a.groups, P);
+  if (!lane_lr) {
+    PYZ_LAUNCH(k_sgld_update_chains, grid, dim3(256), 0, st, a);
+    return;
+  }
+  SgldLanesArgs l{};
+  l.c = a;
+  l.seed_stride = (unsigned)seed_stride;
+  for (int c = 0; c < P; ++c) l.rates.lr[c] = lane_lr[c];
+  PYZ_LAUNCH(k_sgld_update_lanes, grid, dim3(256), 0, st, l);
+}
+
+// One eager step of P chains (lane_lr == nullptr: every chain at lr) or of P lanes (lane c at lane_lr[c]; the StepCtl's
+// rate is lane 0's, the update reads the launch's own).
+static int sgld_rows_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int P, const float *d_x,
+                          const void *d_y, const int32_t *d_row_idx, int batch, float lr, const float *lane_lr, int64_t n,
+                          uint64_t seed, int seed_stride, const float *d_unit_noise, float *d_loss, void *stream) {
+  int rc;
+  if ((rc = check_call(m, P, batch))) return rc;
+  if ((rc = need_grad(m, P))) return rc;
+  hipStream_t st = as_stream(stream);
+  set_ctl_lazy(m, batch, lr, n);   // the first kernel of the pass carries the step scalars
+  launch_sgld_rows_step(m, d_theta, d_mean, d_sq_mean, P, d_x, d_y, d_row_idx, batch, 0, false, 0, seed, lane_lr, seed_stride,
+                        d_unit_noise, d_loss, st);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
 }
 
 int pyz_sgld_chains_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_chains, const float *d_x,
                          const void *d_y, const int32_t *d_row_idx, int batch, float lr, int64_t n, uint64_t seed,
                          const float *d_unit_noise, float *d_loss, void *stream) {
-  int rc = sgld_chains_check(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_loss, n);
-  if (rc) return rc;
-  if ((rc = check_call(m, n_chains, batch))) return rc;
-  if ((rc = need_grad(m, n_chains))) return rc;
-  hipStream_t st = as_stream(stream);
-  set_ctl_lazy(m, batch, lr, n);   // the first kernel of the pass carries the step scalars
-  launch_sgld_chains_step(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, batch, 0, false, 0, seed,
-                          d_unit_noise, d_loss, st);
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  const int rc = sgld_rows_check(m, false, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, nullptr, d_loss, n, 0);
+  return rc ? rc : sgld_rows_step(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, batch, lr, nullptr, n, seed, 0,
+                                  d_unit_noise, d_loss, stream);
+}
+
+int pyz_sgld_lanes_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
+                        const void *d_y, const int32_t *d_row_idx, int batch, const float *h_lr, int64_t n, uint64_t seed,
+                        int seed_stride, const float *d_unit_noise, float *d_loss, void *stream) {
+  const int rc = sgld_rows_check(m, true, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, h_lr, d_loss, n, seed_stride);
+  return rc ? rc : sgld_rows_step(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, batch, h_lr[0], h_lr, n, seed,
+                                  seed_stride, d_unit_noise, d_loss, stream);
 }
 
 // The run enqueues its steps one after the other (no graph: use_graph is accepted and pyz_last_run_info reports every step
 // as eager).  Each step is launched for ITS OWN batch size -- the host has the sizes -- so that its launches are those of
 // pyz_sgld_chains_step, whose weight-gradient launch picks its waves from the batch it is launched for: that is what makes
 // the run equal the step calls bit for bit on ragged batches.  The scalars the kernels read still come from the device
-// tables (StepCtl ping-pong, advanced by k_sgld_update_chains), so nothing waits for the host between two steps.
+// tables (StepCtl ping-pong, advanced by the update kernel), so nothing waits for the host between two steps.
+// Chains: h_lr holds n_steps rates, the device's rate table.  Lanes: h_lr is the host's (n_steps, P) table, row s rides in
+// step s's launch, and the device's rate table gets lane 0's column (nobody reads it: it keeps the StepCtl meaningful).
+static int sgld_rows_run(pyz_mlp *m, bool lanes, float *d_theta, float *d_mean, float *d_sq_mean, int P, const float *d_x,
+                         const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
+                         int n_steps, int64_t n0, int64_t slot0, uint64_t seed, int seed_stride, float *d_losses,
+                         void *stream) {
+  int rc = sgld_rows_check(m, lanes, d_theta, d_mean, d_sq_mean, P, d_x, d_y, h_lr, d_losses, n0, seed_stride);
+  if (rc) return rc;
+  if (!d_row_idx || !h_batch_sizes || !h_lr) return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
+  if ((rc = need_grad(m, P))) return rc;
+  hipStream_t st = as_stream(stream);
+  const long long row_stride = m->max_batch;
+  std::vector<float> lane0;
+  for (int s = 0; lanes && s < n_steps; ++s) lane0.push_back(h_lr[(size_t)s * P]);
+  // the tables go up as pyz_sgld_run sends them; no batch is assembled ahead
+  if ((rc = upload_run_tables(m, h_batch_sizes, lanes ? lane0.data() : h_lr, n_steps, n0, slot0, nullptr, d_x, d_row_idx, 0, st)))
+    return rc;
+  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    launch_sgld_rows_step(m, d_theta, d_mean, d_sq_mean, P, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true, row_stride,
+                          seed, lanes ? h_lr + (size_t)s * P : nullptr, seed_stride, nullptr, d_losses, st);
+    ++m->run_eager_steps;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
 int pyz_sgld_chains_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_chains, const float *d_x,
                         const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
                         int n_steps, int64_t n0, int64_t slot0, uint64_t seed, float *d_losses, int use_graph,
                         void *stream) {
   (void)use_graph;
-  int rc = sgld_chains_check(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_losses, n0);
-  if (rc) return rc;
-  if (!d_row_idx || !h_batch_sizes || !h_lr) return pyz_fail(PYZ_E_INVALID, "null pointer");
-  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
-  if ((rc = need_grad(m, n_chains))) return rc;
-  hipStream_t st = as_stream(stream);
-  const long long row_stride = m->max_batch;
-  // the tables go up as pyz_sgld_run sends them; no batch is assembled ahead
-  if ((rc = upload_run_tables(m, h_batch_sizes, h_lr, n_steps, n0, slot0, nullptr, d_x, d_row_idx, 0, st))) return rc;
-  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
-  for (int s = 0; s < n_steps; ++s) {
-    launch_sgld_chains_step(m, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true,
-                            row_stride, seed, nullptr, d_losses, st);
-    ++m->run_eager_steps;
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  return sgld_rows_run(m, false, d_theta, d_mean, d_sq_mean, n_chains, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, n0,
+                       slot0, seed, 0, d_losses, stream);
 }
 
-// ---- SGLD lanes (pyz_sgld_lanes.h): the chains step with a learning rate per lane and the seed seed + c * seed_stride.
-// The gradient pass is launch_sgld_chains_step's; k_sgld_update_lanes stands where k_sgld_update_chains stands there.
-static int sgld_lanes_check(const pyz_mlp *m, const void *theta, const void *mean, const void *sq, int n_lanes,
-                            const void *x, const void *y, const void *h_lr, const void *losses, int64_t n, int seed_stride) {
-  if (n_lanes < 1) return pyz_fail(PYZ_E_INVALID, "n_lanes %d: at least one lane", n_lanes);
-  if (n < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
-  if (seed_stride != 0 && seed_stride != 1)
-    return pyz_fail(PYZ_E_INVALID, "seed_stride %d: 0 (one noise stream for every lane) or 1 (seed + lane)", seed_stride);
-  if (!theta || !mean || !sq || !x || !y || !h_lr || !losses) return pyz_fail(PYZ_E_INVALID, "null pointer");
-  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
-  if (n_lanes > m->max_p || n_lanes > PYZ_MAX_LANES)
-    return pyz_fail(PYZ_E_SHAPE, "n_lanes %d outside [1, %d] of the plan and the library", n_lanes, std::min(m->max_p, PYZ_MAX_LANES));
-  return check_loss_combo(m);
-}
-
-static void launch_sgld_lanes_step(pyz_mlp *m, float *theta, float *mean, float *sq, int P, const float *x, const void *y,
-                                   const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
-                                   const float *h_lr, uint64_t seed, int seed_stride, const float *unit_noise, float *loss,
-                                   hipStream_t st) {
-  const StepCtl *ctl = m->ctl + slot;
-  WgradArgs u{};
-  u.mode = PYZ_UPD_NONE;
-  u.grad = m->grad;
-  u.grad_pstride = m->D;
-  const bool fused = can_fuse(m);
-  if (fused) u.ploss = m->scal;
-  launch_loss_backward(m, theta, m->D, P, x, y, row_idx, grid_batch, ctl, true, u, st);
-  if (!fused) PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, ctl, m->scal, m->nonfinite);
-  SgldLanesArgs a{};
-  a.c.theta = theta;
-  a.c.mean = mean;
-  a.c.sq_mean = sq;
-  a.c.grad = m->grad;
-  a.c.D = m->D;
-  a.c.grad_pstride = m->D;
-  a.c.groups = (m->D + 3) / 4;
-  a.c.ctl = ctl;
-  a.c.next = chained ? m->ctl + (slot ^ 1) : nullptr;
-  a.c.tab_bs = m->tab_bs;
-  a.c.tab_lr = m->tab_lr;
-  a.c.row_stride = row_stride;
-  a.c.seed = seed;
-  a.c.unit_noise = unit_noise;
-  a.c.ploss = m->scal;
-  a.c.loss = loss;
-  a.c.loss_indexed = chained ? 1 : 0;
-  a.seed_stride = (unsigned)seed_stride;
-  for (int c = 0; c < P; ++c) a.rates.lr[c] = h_lr[c];
-  // the chains kernel's grid rule: the launch fills the chip once
-  const long long per_lane = std::max<long long>(1, 8LL * pyz_cu_count() / P);
-  const dim3 grid((unsigned)std::min<long long>(cdiv(a.c.groups, 256), per_lane), (unsigned)P);
-  PYZ_LAUNCH(k_sgld_update_lanes, grid, dim3(256), 0, st, a);
-}
-
-int pyz_sgld_lanes_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
-                        const void *d_y, const int32_t *d_row_idx, int batch, const float *h_lr, int64_t n, uint64_t seed,
-                        int seed_stride, const float *d_unit_noise, float *d_loss, void *stream) {
-  int rc = sgld_lanes_check(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, h_lr, d_loss, n, seed_stride);
-  if (rc) return rc;
-  if ((rc = check_call(m, n_lanes, batch))) return rc;
-  if ((rc = need_grad(m, n_lanes))) return rc;
-  hipStream_t st = as_stream(stream);
-  set_ctl_lazy(m, batch, h_lr[0], n);   // (the StepCtl's rate is lane 0's; the update reads the launch's own)
-  launch_sgld_lanes_step(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, batch, 0, false, 0, h_lr, seed,
-                         seed_stride, d_unit_noise, d_loss, st);
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
-}
-
-// As pyz_sgld_chains_run: every step enqueued for its own batch size, the scalars from the StepCtl ping-pong; the rates
-// of step s are row s of the host's (n_steps, n_lanes) table, in that step's launch.  The device's rate table gets lane
-// 0's column (nobody reads it: it keeps the StepCtl meaningful).
 int pyz_sgld_lanes_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int n_lanes, const float *d_x,
                        const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
                        int n_steps, int64_t n0, int64_t slot0, uint64_t seed, int seed_stride, float *d_losses,
                        void *stream) {
-  int rc = sgld_lanes_check(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, h_lr, d_losses, n0, seed_stride);
-  if (rc) return rc;
-  if (!d_row_idx || !h_batch_sizes) return pyz_fail(PYZ_E_INVALID, "null pointer");
-  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
-  if ((rc = need_grad(m, n_lanes))) return rc;
-  hipStream_t st = as_stream(stream);
-  const long long row_stride = m->max_batch;
-  std::vector<float> lane0((size_t)n_steps);
-  for (int s = 0; s < n_steps; ++s) lane0[s] = h_lr[(size_t)s * n_lanes];
-  if ((rc = upload_run_tables(m, h_batch_sizes, lane0.data(), n_steps, n0, slot0, nullptr, d_x, d_row_idx, 0, st))) return rc;
-  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
-  for (int s = 0; s < n_steps; ++s) {
-    launch_sgld_lanes_step(m, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true,
-                           row_stride, h_lr + (size_t)s * n_lanes, seed, seed_stride, nullptr, d_losses, st);
-    ++m->run_eager_steps;
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  return sgld_rows_run(m, true, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, n0,
+                       slot0, seed, seed_stride, d_losses, stream);
 }
 
+// ---- the scores of SGLD lanes (pyz_sgld_lanes.h)
 // The loss sum (and wrong rows) of every lane over n rows: one particle-batched forward per chunk of max_particles lanes,
 // as pyz_predict, with the last layer left at its logits where the loss head starts from them (one sigmoid unit), and
 // k_lane_scores over m->act[L - 1].

@@ -73,9 +73,12 @@ __device__ __forceinline__ void pyz_st4(float *p, const bool wide, const int nv,
   }
 }
 
-__global__ void __launch_bounds__(256) k_sgld_update_chains(SgldChainsArgs g) {
-  const long long c = blockIdx.y;
-  const float lr = g.ctl->lr;
+// Row c of the (P, D) state with the rate and the noise seed its kernel gives it, and the row's duties: everything
+// k_sgld_update_chains and k_sgld_update_lanes (pyz_sgld_lanes.h) do behind those two values.  `block` is the kernel's
+// blockDim.x: only a __global__ function's own read of it compiles to the plain load of the workgroup size (a device
+// function's also selects the remainder size of a ragged grid, one more load ahead of the loop).
+__device__ __forceinline__ void pyz_sgld_update_row(const SgldChainsArgs &g, const long long c, const float lr,
+                                                    const uint64_t seed, const unsigned block) {
   const long long n = g.ctl->n;
   const float fn = (float)n, fn1 = fn + 1.0f;
   float *th_row = g.theta + c * g.D, *mu_row = g.mean + c * g.D, *sq_row = g.sq_mean + c * g.D;
@@ -84,9 +87,8 @@ __global__ void __launch_bounds__(256) k_sgld_update_chains(SgldChainsArgs g) {
   // a group starts 16 bytes x t behind its row: the row's alignment is the group's
   const bool a_th = pyz_row_aligned16(th_row), a_mu = pyz_row_aligned16(mu_row), a_sq = pyz_row_aligned16(sq_row);
   const bool a_gr = pyz_row_aligned16(gr_row), a_nz = nz_row && pyz_row_aligned16(nz_row);
-  const uint64_t seed = g.seed + (uint64_t)c;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < g.groups; t += stride) {
+  const long long stride = (long long)gridDim.x * block;
+  for (long long t = (long long)blockIdx.x * block + threadIdx.x; t < g.groups; t += stride) {
     const long long e0 = 4 * t;
     const long long left = g.D - e0;
     const int nv = left >= 4 ? 4 : (int)left;
@@ -119,4 +121,9 @@ __global__ void __launch_bounds__(256) k_sgld_update_chains(SgldChainsArgs g) {
     lo[c] = g.ploss[c];
     if (c == 0 && g.next) pyz_prepare_next(g.ctl, g.next, g.tab_bs, g.tab_lr, g.row_stride);
   }
+}
+
+__global__ void __launch_bounds__(256) k_sgld_update_chains(SgldChainsArgs g) {
+  const long long c = blockIdx.y;
+  pyz_sgld_update_row(g, c, g.ctl->lr, g.seed + (uint64_t)c, blockDim.x);
 }

@@ -1,12 +1,10 @@
 // pyz_sgld_lanes.h -- P SGLD chains that differ by their hyper-parameters ("lanes": pyz_sgld_lanes_step / _run), and the
 // score of every lane on a data split (pyz_lane_scores).
 //
-// k_sgld_update_lanes is k_sgld_update_chains (pyz_sgld_chains.h) with two things per lane instead of per launch:
+// k_sgld_update_lanes runs the chains kernel's body, pyz_sgld_update_row (pyz_sgld_chains.h: expressions, layout,
+// alignment rule, grid and duties are described there), with two things per lane instead of per launch:
 //   lr   = lr[c]                     (the chains kernel: ctl->lr for every chain)
 //   seed = seed + c * seed_stride    (the chains kernel: seed + c), seed_stride in {0, 1}
-// and the same float32 expressions in the same order behind them:
-//   noise = lr * z;  theta[c][e] += -lr * (grad[c][e] + noise)
-//   mean[c][e] <- (mean[c][e] * n + theta) / (n + 1);  sq_mean[c][e] <- (sq_mean[c][e] * n + theta^2) / (n + 1)
 // With every lr[c] equal to ctl->lr and seed_stride = 1 a lanes step is a chains step bit for bit.  seed_stride = 0 gives
 // every lane ONE noise stream (common random numbers): two lanes with equal starts and equal rates stay equal, and lanes
 // that differ by their rates alone are compared on the same draws.
@@ -15,9 +13,6 @@
 // s's launch carries row s of the host's (n_steps, P) table): a fixed array of PYZ_MAX_LANES floats indexed by blockIdx.y,
 // no second device table and nothing to stage.  n, the batch and the loss slot still come from the StepCtl, which lane 0
 // advances for the next step as chain 0 does.
-//
-// Layout, alignment rule (per buffer and per row, the last partial group element by element), grid and duties are those
-// of the chains kernel; pyz_ld4 / pyz_st4 / pyz_row_aligned16 are its helpers.
 //
 // k_lane_scores: thread = row of the split, grid (ceil(n / 256), lanes).  The per-row loss is the plan's loss head's, in
 // its float32 expressions, from the last layer's logits (softmax, one sigmoid unit) or outputs (MSE); a workgroup adds
@@ -43,51 +38,8 @@ struct SgldLanesArgs {
 };
 
 __global__ void __launch_bounds__(256) k_sgld_update_lanes(SgldLanesArgs a) {
-  const SgldChainsArgs &g = a.c;
   const long long c = blockIdx.y;
-  const float lr = a.rates.lr[c];
-  const long long n = g.ctl->n;
-  const float fn = (float)n, fn1 = fn + 1.0f;
-  float *th_row = g.theta + c * g.D, *mu_row = g.mean + c * g.D, *sq_row = g.sq_mean + c * g.D;
-  const float *gr_row = g.grad + c * g.grad_pstride;
-  const float *nz_row = g.unit_noise ? g.unit_noise + c * g.D : nullptr;
-  const bool a_th = pyz_row_aligned16(th_row), a_mu = pyz_row_aligned16(mu_row), a_sq = pyz_row_aligned16(sq_row);
-  const bool a_gr = pyz_row_aligned16(gr_row), a_nz = nz_row && pyz_row_aligned16(nz_row);
-  const uint64_t seed = g.seed + (uint64_t)c * (uint64_t)a.seed_stride;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < g.groups; t += stride) {
-    const long long e0 = 4 * t;
-    const long long left = g.D - e0;
-    const int nv = left >= 4 ? 4 : (int)left;
-    const bool full = nv == 4;
-    float z[4], th[4], mu[4], sq[4], gv[4];
-    if (nz_row) {
-      pyz_ld4(nz_row + e0, a_nz && full, nv, z);
-    } else {
-      const float4 q = pyz_normal4(seed, PYZ_STREAM_SGLD, (uint32_t)n, (uint64_t)t);
-      z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w;
-    }
-    pyz_ld4(th_row + e0, a_th && full, nv, th);
-    pyz_ld4(gr_row + e0, a_gr && full, nv, gv);
-    pyz_ld4(mu_row + e0, a_mu && full, nv, mu);
-    pyz_ld4(sq_row + e0, a_sq && full, nv, sq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float noise = lr * z[j];
-      const float t1 = th[j] + (-lr) * (gv[j] + noise);
-      th[j] = t1;
-      mu[j] = (mu[j] * fn + t1) / fn1;
-      sq[j] = (sq[j] * fn + t1 * t1) / fn1;
-    }
-    pyz_st4(th_row + e0, a_th && full, nv, th);
-    pyz_st4(mu_row + e0, a_mu && full, nv, mu);
-    pyz_st4(sq_row + e0, a_sq && full, nv, sq);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    float *lo = g.loss + (g.loss_indexed ? (long long)(g.ctl->slot0 + g.ctl->i) * gridDim.y : 0);
-    lo[c] = g.ploss[c];
-    if (c == 0 && g.next) pyz_prepare_next(g.ctl, g.next, g.tab_bs, g.tab_lr, g.row_stride);
-  }
+  pyz_sgld_update_row(a.c, c, a.rates.lr[c], a.c.seed + (uint64_t)c * (uint64_t)a.seed_stride, blockDim.x);
 }
 
 // ---------------------------------------------------------------- scores

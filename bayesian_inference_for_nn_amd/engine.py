@@ -246,15 +246,33 @@ class MLPPlan:
             _f32(t, (P, self.D), nm)
         return P
 
-    def sgld_chains_step(self, theta, mean, sq_mean, x, y, lr, n, seed, loss_out, batch=None, row_idx=None, unit_noise=None):
-        """One SGLD step of the n_chains rows of theta / mean / sq_mean (n_chains, D) on ONE shared batch; chain c draws
-        the noise of seed + c (or row c of the (n_chains, D) unit_noise); loss_out: (n_chains,) float32."""
-        P = self._check_chains(theta, mean, sq_mean)
+    def _check_rows_step(self, P, x, y, loss_out, batch, row_idx, unit_noise):
+        """The noise, the losses and the batch of one step of P chains or lanes; returns the batch size."""
         if unit_noise is not None:
             _f32(unit_noise, (P, self.D), "unit_noise")
         _f32(loss_out, (P,), "loss_out")
         batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
         self._check_xy(x, y, row_idx, batch)
+        return batch
+
+    def _check_rows_run(self, P, rows, x, y, row_idx, batch_sizes, losses_out, slot0):
+        """The tables of a run of P chains or lanes (`rows`: "n_chains" / "n_lanes"); returns the c_int32 batch sizes."""
+        n_steps = len(batch_sizes)
+        self._check_xy(x, y, row_idx, 1)
+        if slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch:
+            raise ValueError("row_idx must hold (slot0 + n_steps) * max_batch entries")
+        _f32(losses_out, name="losses_out")
+        if losses_out.numel() < (slot0 + n_steps) * P:
+            raise ValueError(f"losses_out must hold (slot0 + n_steps) * {rows} entries")
+        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
+            raise ValueError("batch size outside the plan")
+        return (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes])
+
+    def sgld_chains_step(self, theta, mean, sq_mean, x, y, lr, n, seed, loss_out, batch=None, row_idx=None, unit_noise=None):
+        """One SGLD step of the n_chains rows of theta / mean / sq_mean (n_chains, D) on ONE shared batch; chain c draws
+        the noise of seed + c (or row c of the (n_chains, D) unit_noise); loss_out: (n_chains,) float32."""
+        P = self._check_chains(theta, mean, sq_mean)
+        batch = self._check_rows_step(P, x, y, loss_out, batch, row_idx, unit_noise)
         check(self.lib.pyz_sgld_chains_step(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx),
                                             batch, float(lr), int(n), int(seed), ptr(unit_noise), ptr(loss_out), _stream()))
 
@@ -265,15 +283,7 @@ class MLPPlan:
         P = self._check_chains(theta, mean, sq_mean)
         n_steps = len(batch_sizes)
         assert len(lrs) == n_steps and n_steps > 0
-        self._check_xy(x, y, row_idx, 1)
-        if slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch:
-            raise ValueError("row_idx must hold (slot0 + n_steps) * max_batch entries")
-        _f32(losses_out, name="losses_out")
-        if losses_out.numel() < (slot0 + n_steps) * P:
-            raise ValueError("losses_out must hold (slot0 + n_steps) * n_chains entries")
-        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
-            raise ValueError("batch size outside the plan")
-        bs = (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes])
+        bs = self._check_rows_run(P, "n_chains", x, y, row_idx, batch_sizes, losses_out, slot0)
         lr = (C.c_float * n_steps)(*[float(v) for v in lrs])
         check(self.lib.pyz_sgld_chains_run(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx), bs,
                                            lr, n_steps, int(n0), int(slot0), int(seed), ptr(losses_out),
@@ -299,11 +309,7 @@ class MLPPlan:
         """sgld_chains_step with a rate per lane (lrs: P host floats) and the seed seed + c * seed_stride for lane c."""
         P = self._check_lanes(theta, mean, sq_mean, seed_stride)
         lr = self._lane_rates(lrs, (P,))
-        if unit_noise is not None:
-            _f32(unit_noise, (P, self.D), "unit_noise")
-        _f32(loss_out, (P,), "loss_out")
-        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
-        self._check_xy(x, y, row_idx, batch)
+        batch = self._check_rows_step(P, x, y, loss_out, batch, row_idx, unit_noise)
         check(self.lib.pyz_sgld_lanes_step(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx), batch,
                                            lr.ctypes.data_as(C.POINTER(C.c_float)), int(n), int(seed), int(seed_stride),
                                            ptr(unit_noise), ptr(loss_out), _stream()))
@@ -317,15 +323,7 @@ class MLPPlan:
         if n_steps < 1:
             raise ValueError("at least one step")
         lr = self._lane_rates(lrs, (n_steps, P))
-        self._check_xy(x, y, row_idx, 1)
-        if slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch:
-            raise ValueError("row_idx must hold (slot0 + n_steps) * max_batch entries")
-        _f32(losses_out, name="losses_out")
-        if losses_out.numel() < (slot0 + n_steps) * P:
-            raise ValueError("losses_out must hold (slot0 + n_steps) * n_lanes entries")
-        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
-            raise ValueError("batch size outside the plan")
-        bs = (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes])
+        bs = self._check_rows_run(P, "n_lanes", x, y, row_idx, batch_sizes, losses_out, slot0)
         check(self.lib.pyz_sgld_lanes_run(self.h, ptr(theta), ptr(mean), ptr(sq_mean), P, ptr(x), ptr(y), ptr(row_idx), bs,
                                           lr.ctypes.data_as(C.POINTER(C.c_float)), n_steps, int(n0), int(slot0), int(seed),
                                           int(seed_stride), ptr(losses_out), _stream()))

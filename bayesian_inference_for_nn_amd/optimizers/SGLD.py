@@ -221,34 +221,23 @@ class SGLD(Optimizer):
     def _train_resident(self, nb_iterations: int) -> bool:
         """verbose=False: all steps in one device-resident run (hipGraph replay, no host sync)."""
         import torch
+        rows = self._lanes is not None or self._n_chains > 1       # a (P, D) state: the loss buffer holds a row per step
         if self._lanes is not None:
             rates = self._lane_rates(self._n, nb_iterations)
 
-            def launch_lanes(idx, loss_buf, sizes, s0):
+            def launch(idx, loss_buf, sizes, s0):
                 self._plan.sgld_lanes_run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
                                           rates[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf,
                                           seed_stride=self._lane_stride, slot0=s0)
-            losses = self._run_resident_chunks(nb_iterations, launch_lanes)           # (nb_iterations, P)
-            self._running_dev += losses.mean(dim=1).sum()
-            self._n += nb_iterations
-            self.last_losses = losses.clone()
-            return True
-        lrs = np.asarray(self._lr(self._n + np.arange(nb_iterations, dtype=np.float64))).astype(np.float32).tolist()
-        if self._n_chains > 1:
-            def launch_chains(idx, loss_buf, sizes, s0):
-                self._plan.sgld_chains_run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
-                                           lrs[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf, use_graph=True, slot0=s0)
-            losses = self._run_resident_chunks(nb_iterations, launch_chains)          # (nb_iterations, P)
-            self._running_dev += losses.mean(dim=1).sum()
-            self._n += nb_iterations
-            self.last_losses = losses.clone()
-            return True
+        else:
+            lrs = np.asarray(self._lr(self._n + np.arange(nb_iterations, dtype=np.float64))).astype(np.float32).tolist()
+            run = self._plan.sgld_chains_run if rows else self._plan.sgld_run
 
-        def launch(idx, loss_buf, sizes, s0):
-            self._plan.sgld_run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
-                                lrs[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf, use_graph=True, slot0=s0)
+            def launch(idx, loss_buf, sizes, s0):
+                run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
+                    lrs[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf, use_graph=True, slot0=s0)
         losses = self._run_resident_chunks(nb_iterations, launch)
-        self._running_dev += losses.sum()
+        self._running_dev += losses.mean(dim=1).sum() if rows else losses.sum()   # rows: the mean over chains of a step
         self._n += nb_iterations
         self.last_losses = losses.clone()          # the buffer itself is reused by the next run
         return True

@@ -295,6 +295,44 @@ def test_run_equals_step_calls_bit_for_bit(eng, shape, stride):
     plan.close()
 
 
+@pytest.mark.parametrize("name", ("f_d25_odd_p2", "f_d66_gathered_p5"))
+def test_lanes_run_with_equal_rates_is_the_chains_run_bit_for_bit(eng, name):
+    """Three steps with batches (full, full - 2, full) from the case's start, the device drawing the noise: sgld_lanes_run
+    with seed_stride 1 and every lane of step s at the chains run's lrs[s] leaves theta, mean, sq_mean and the (3, P) loss
+    rows of sgld_chains_run bit for bit, and both report three eager steps and no graph launch."""
+    case = lc.CASE_BY_NAME[name]
+    data = lc.chains_data(case)
+    s0 = lc.initial_state(data)
+    run = Run(eng, case, data)
+    st, P = case.step, case.P
+    sizes = [st.batch, st.batch - 2, st.batch]
+    rows = data.step.idx if data.step.idx is not None else np.arange(st.batch)
+    table = np.zeros((3, st.max_batch), dtype=np.int32)
+    table[:, :st.batch] = rows[:st.batch]
+    table_dev = dev(table, torch.int32)
+    lrs = [float(np.float32(st.lr / (1.0 + 0.25 * s))) for s in range(3)]        # a rate per step, all different
+    rates = np.repeat(np.asarray(lrs, dtype=np.float32)[:, None], P, axis=1)
+    b, got = run.bufs, {}
+    for which in ("chains", "lanes"):
+        run.set_state(s0)
+        losses = Guarded(np.full((3, P), SENTINEL), True)
+        if which == "chains":
+            run.plan.sgld_chains_run(b["theta"].t, b["mean"].t, b["sq"].t, run.x, run.y, table_dev, sizes, lrs, st.n0, st.seed,
+                                     losses.t)
+        else:
+            run.plan.sgld_lanes_run(b["theta"].t, b["mean"].t, b["sq"].t, run.x, run.y, table_dev, sizes, rates, st.n0, st.seed,
+                                    losses.t, seed_stride=1)
+        assert run.plan.last_run_path() == ("eager", 3) and run.plan.last_run_graph_launches() == 0, which
+        got[which] = run.get_state()
+        got[which]["loss"] = losses.get()
+        assert losses.intact() and run.guards_broken() == [], which
+    assert np.all(np.isfinite(got["chains"]["loss"])) and not np.array_equal(bits(got["chains"]["theta"]), bits(s0["theta"]))
+    for key in ("theta", "mean", "sq", "loss"):
+        assert np.array_equal(bits(got["lanes"][key]), bits(got["chains"][key])), f"{name}: {key} differs from sgld_chains_run"
+    run.plan.check_finite()
+    run.plan.close()
+
+
 def test_shape_errors(eng):
     from bayesian_inference_for_nn_amd._lib import PyzError, check, ptr
     import ctypes as C
