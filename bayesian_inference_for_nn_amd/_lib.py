@@ -19,6 +19,7 @@ STREAM_PILCO = 8           # PYZ_STREAM_PILCO
 STREAM_FSVI = 9            # PYZ_STREAM_FSVI (csrc/pyz_rng.h)
 FSVI_MAX_N, FSVI_MAX_D = 1024, 2048    # PYZ_FSVI_MAX_N / PYZ_FSVI_MAX_D
 REWARD = {"Cart": 0, "Acb 2 factors": 1}    # PYZ_REWARD_*; the names of dynamics.all_rewards
+PILCO_KIND = {"dense": 0, "rbf": 1}         # PYZ_PILCO_*
 
 
 class PyzError(RuntimeError):
@@ -99,10 +100,13 @@ SIGNATURES = {
     "pyz_score_rows": (C.c_int, [_p, C.c_int, _i64, C.c_int, _p, C.c_int, _p, _p]),
     "pyz_pilco_create": (C.c_int, [C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int,
                                    C.c_int, C.POINTER(_p)]),
+    "pyz_pilco_create_layers": (C.c_int, [C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f), C.c_int,
+                                          C.POINTER(_i32), C.POINTER(_i32), C.c_int, C.c_int, C.POINTER(_p)]),
     "pyz_pilco_destroy": (C.c_int, [_p]),
     "pyz_pilco_workspace_bytes": (_i64, [_p]),
     "pyz_pilco_policy_step": (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _p, C.c_int, C.c_int, _f, C.c_int, _f, _p, _p, _p, _p,
                                         C.c_int, _p]),
+    "pyz_pilco_act": (C.c_int, [_p, _p, _p, C.c_int, _p, _p]),
     "pyz_sample_normal_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _u64, _u32, _u32, _p]),
     "pyz_sample_lowrank_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _f, _u64, _u32, _u32, _p]),
     "pyz_gather_rows": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p]),

@@ -3228,8 +3228,10 @@ struct pyz_pilco {
   PyzGraphCache<4> graphs;       // one graph per (H, freq); everything else baked into them is the cache's key
 };
 
-static int pilco_net(PilcoNet &net, const char *what, int L, const int32_t *dims, const int32_t *acts, bool softmax_last) {
-  if (!dims || !acts) return pyz_fail(PYZ_E_INVALID, "null argument");
+// kinds / gammas: one entry per layer, or null: every layer Dense
+static int pilco_net(PilcoNet &net, const char *what, int L, const int32_t *dims, const int32_t *acts, bool softmax_last,
+                     const int32_t *kinds, const float *gammas) {
+  if (!dims || !acts || (kinds && !gammas)) return pyz_fail(PYZ_E_INVALID, "null argument");
   if (L < 1 || L > PILCO_MAX_LAYERS) return pyz_fail(PYZ_E_INVALID, "%s: %d layers outside [1, %d]", what, L, PILCO_MAX_LAYERS);
   net.L = L;
   int off = 0;
@@ -3240,11 +3242,24 @@ static int pilco_net(PilcoNet &net, const char *what, int L, const int32_t *dims
   }
   for (int l = 0; l < L; ++l) {
     const bool last = l == L - 1;
+    const int kind = kinds ? kinds[l] : PYZ_PILCO_DENSE;
+    if (kind != PYZ_PILCO_DENSE && kind != PYZ_PILCO_RBF) return pyz_fail(PYZ_E_INVALID, "%s: unknown kind %d of layer %d", what, kind, l);
     if (acts[l] < PYZ_ACT_LINEAR || acts[l] > PYZ_ACT_SOFTMAX || (acts[l] == PYZ_ACT_SOFTMAX && !(last && softmax_last)))
       return pyz_fail(PYZ_E_INVALID, "%s: activation %d at layer %d is not supported", what, acts[l], l);
     net.acts[l] = acts[l];
+    net.kind[l] = kind;
+    net.gamma[l] = 0.0f;
     net.w_off[l] = off;
-    off += (dims[l] + 1) * dims[l + 1];
+    if (kind == PYZ_PILCO_RBF) {
+      if (last) return pyz_fail(PYZ_E_INVALID, "%s: an RBF layer cannot be the last layer", what);
+      if (!std::isfinite(gammas[l]) || !(gammas[l] > 0.0f))
+        return pyz_fail(PYZ_E_INVALID, "%s: gamma %g of RBF layer %d is not a finite number > 0", what, (double)gammas[l], l);
+      if (acts[l] != PYZ_ACT_LINEAR) return pyz_fail(PYZ_E_INVALID, "%s: RBF layer %d takes no activation (pass linear)", what, l);
+      net.gamma[l] = gammas[l];
+      off += dims[l] * dims[l + 1];                  // the means: no bias
+    } else {
+      off += (dims[l] + 1) * dims[l + 1];
+    }
   }
   return PYZ_OK;
 }
@@ -3252,12 +3267,27 @@ static int pilco_net(PilcoNet &net, const char *what, int L, const int32_t *dims
 int pyz_pilco_create(int n_policy_layers, const int32_t *h_policy_dims, const int32_t *h_policy_acts, int n_dynamics_layers,
                      const int32_t *h_dynamics_dims, const int32_t *h_dynamics_acts, int particles, int max_horizon,
                      pyz_pilco **out) {
+  int32_t kinds[PILCO_MAX_LAYERS];                 // (pilco_net reads the first n_policy_layers, once it has checked that count)
+  float gammas[PILCO_MAX_LAYERS];
+  for (int l = 0; l < PILCO_MAX_LAYERS; ++l) {
+    kinds[l] = PYZ_PILCO_DENSE;
+    gammas[l] = 0.0f;
+  }
+  return pyz_pilco_create_layers(n_policy_layers, h_policy_dims, h_policy_acts, kinds, gammas, n_dynamics_layers, h_dynamics_dims,
+                                 h_dynamics_acts, particles, max_horizon, out);
+}
+
+int pyz_pilco_create_layers(int n_policy_layers, const int32_t *h_policy_dims, const int32_t *h_policy_acts,
+                            const int32_t *h_policy_kinds, const float *h_policy_gammas, int n_dynamics_layers,
+                            const int32_t *h_dynamics_dims, const int32_t *h_dynamics_acts, int particles, int max_horizon,
+                            pyz_pilco **out) {
   if (!out) return pyz_fail(PYZ_E_INVALID, "null argument");
   *out = nullptr;
+  if (!h_policy_kinds || !h_policy_gammas) return pyz_fail(PYZ_E_INVALID, "null argument");
   PilcoArgs a{};
   int rc;
-  if ((rc = pilco_net(a.pol, "policy", n_policy_layers, h_policy_dims, h_policy_acts, true))) return rc;
-  if ((rc = pilco_net(a.dyn, "dynamics", n_dynamics_layers, h_dynamics_dims, h_dynamics_acts, false))) return rc;
+  if ((rc = pilco_net(a.pol, "policy", n_policy_layers, h_policy_dims, h_policy_acts, true, h_policy_kinds, h_policy_gammas))) return rc;
+  if ((rc = pilco_net(a.dyn, "dynamics", n_dynamics_layers, h_dynamics_dims, h_dynamics_acts, false, nullptr, nullptr))) return rc;
   if (a.dyn.acts[a.dyn.L - 1] != PYZ_ACT_LINEAR)
     return pyz_fail(PYZ_E_INVALID, "the dynamics' last layer must be linear, not activation %d", a.dyn.acts[a.dyn.L - 1]);
   if (particles < 2 || particles > PILCO_MAX_K)
@@ -3402,6 +3432,17 @@ int pyz_pilco_policy_step(pyz_pilco *p, float *d_phi, float *d_m, float *d_v, in
   p->graphs.rekey(key);
   p->graphs.begin_call();
   return p->graphs.launch(H, (unsigned long long)freq, 0, 4, st, chain);
+}
+
+int pyz_pilco_act(pyz_pilco *p, const float *d_phi, const float *d_states, int N, float *d_actions, void *stream) {
+  if (!p) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (N < 1) return pyz_fail(PYZ_E_INVALID, "%d state rows: at least one is needed", N);
+  if (!d_phi || !d_states || !d_actions) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  PilcoArgs a = p->a;
+  a.phi = d_phi;
+  PYZ_LAUNCH(k_pilco_act, dim3(N), dim3(PILCO_THREADS), pilco_act_lds(a.maxw), as_stream(stream), a, d_states, d_actions);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
 }
 
 // ---------------------------------------------------------------- measurement hook

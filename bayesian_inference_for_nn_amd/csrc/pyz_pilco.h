@@ -13,7 +13,8 @@
 //   k_pilco_set    the scalars of the call (Adam's step size, the per-step cost factors c_t = -gamma^(t / freq) / K, or 0
 //                  for a step that is not counted, c_0 = -1 / K) into device memory, so that a captured graph of the
 //                  other launches serves every call with the same pointers, H and freq; and the TRANSPOSE of every
-//                  Dense kernel of phi and of the K draws (32 x 32 tiles through LDS), for the backward kernels
+//                  kernel (an RBF layer's means too) of phi and of the K draws (32 x 32 tiles through LDS), for the
+//                  backward kernels
 //   k_pilco_fwd    step t = 1..H: workgroup i stages the K x S raw predictions y of step t - 1 in LDS, column c's thread
 //                  sums them in particle order (every workgroup gets the same m and sd), forms s_{t-1,i}, its reward, runs
 //                  the policy and its draw of the dynamics with the activations in LDS, and leaves y_t,i and the tape:
@@ -36,8 +37,17 @@
 // shape (9 -> 512 -> 256 -> 6, K = 32) against 19 us for k_pilco_fwd; the transposition costs one pass over the weights
 // per policy update.  Loads are unconditional (indices clamped): a load under a branch is waited for at the branch's join.
 //
+// The RBF layer (deep_pilco.py:28-51), a hidden layer of the policy only: h[n] = exp(-gamma sum_k (x[k] - mean[k][n])^2),
+// `mean` (in, units) row-major at the layer's offset of phi, no bias (the layer takes in * units floats), gamma a
+// constant of the layer.  Forward: pilco_rbf, the access pattern of pilco_gemv.  Backward, with delta the gradient with
+// respect to h and e[n] = 2 gamma delta[n] h[n]:  d mean[k][n] = e[n] (x[k] - mean[k][n]),  d x[k] = -sum_n e[n] (x[k] -
+// mean[k][n]), the latter one pass over the transposed means of k_pilco_set (pilco_rbf_dx); the h factor is taken there,
+// so no activation gradient follows an RBF layer.  The branch on the layer kind is the same in every thread of a launch.
+//
+// k_pilco_act is the policy alone for N given states, a workgroup per row, through the same pilco_policy as k_pilco_fwd.
+//
 // Limits (checked on the host, before any launch): 2 <= K <= 256, 1 <= S, 1 <= A, S + A <= 64, layer widths <= 512, at most
-// PILCO_MAX_LAYERS Dense layers per net, H <= max_horizon <= 4096.
+// PILCO_MAX_LAYERS layers per net, the policy's last layer Dense, H <= max_horizon <= 4096.
 #pragma once
 
 #include "pyz_common.h"
@@ -55,8 +65,10 @@
 struct PilcoNet {
   int L;
   int dims[PILCO_MAX_LAYERS + 1];
-  int acts[PILCO_MAX_LAYERS];
-  int w_off[PILCO_MAX_LAYERS];   // layer l's kernel (bias follows) in the flat vector
+  int acts[PILCO_MAX_LAYERS];    // (linear for an RBF layer)
+  int w_off[PILCO_MAX_LAYERS];   // layer l's kernel (a Dense layer's bias follows) in the flat vector
+  int kind[PILCO_MAX_LAYERS];    // PYZ_PILCO_DENSE: (in + 1) * out floats; PYZ_PILCO_RBF: the means, in * out floats
+  float gamma[PILCO_MAX_LAYERS]; // of an RBF layer
 };
 
 struct PilcoCtl {
@@ -87,8 +99,9 @@ struct PilcoArgs {
   int t;
 };
 
-// LDS floats of the two step kernels
+// LDS bytes of the two step kernels and of k_pilco_act
 static inline size_t pilco_fwd_lds(int K, int S, int maxw) { return sizeof(float) * ((size_t)K * S + PILCO_MAX_IN + 2 * (size_t)maxw + PILCO_THREADS); }
+static inline size_t pilco_act_lds(int maxw) { return sizeof(float) * (PILCO_MAX_IN + 2 * (size_t)maxw + PILCO_THREADS); }
 static inline size_t pilco_bwd_lds(int K, int S, int maxw, int pw) {
   return sizeof(float) * (2 * (size_t)K * S + PILCO_MAX_IN + (size_t)pw + 2 * (size_t)maxw + PILCO_THREADS);
 }
@@ -150,6 +163,85 @@ __device__ __forceinline__ void pilco_gemv(const float *__restrict__ w, const fl
   __syncthreads();
 }
 
+// out[n] = exp(-gamma sum_k (in[k] - w[k][n])^2) for n < N, w (Kin, N) row-major: pilco_gemv's walk over the means, its
+// split over thread groups and its order of the partial sums.  Ends with a barrier.
+__device__ __forceinline__ void pilco_rbf(const float *__restrict__ w, float gamma, int Kin, int N, const float *in, float *out,
+                                          float *part) {
+  const int tid = threadIdx.x;
+  if (N > PILCO_THREADS / 2) {
+    for (int n0 = 0; n0 < N; n0 += PILCO_THREADS) {
+      const int n = min(n0 + tid, N - 1);
+      const float *col = w + n;
+      float acc = 0.0f;
+#pragma unroll 16
+      for (int k = 0; k < Kin; ++k) {
+        const float d = in[k] - col[(long long)k * N];
+        acc = fmaf(d, d, acc);
+      }
+      if (n0 + tid < N) out[n0 + tid] = expf(-gamma * acc);
+    }
+  } else {
+    int NP = 1;
+    while (NP < N) NP <<= 1;
+    const int G = PILCO_THREADS / NP, gi = tid / NP, n = tid % NP;
+    const int len = (Kin + G - 1) / G;
+    const int k0 = min(gi * len, Kin), k1 = min(k0 + len, Kin);
+    const float *col = w + min(n, N - 1);
+    float acc = 0.0f;
+#pragma unroll 16
+    for (int k = k0; k < k1; ++k) {
+      const float d = in[k] - col[(long long)k * N];
+      acc = fmaf(d, d, acc);
+    }
+    part[tid] = acc;                                  // tid = gi * NP + n
+    __syncthreads();
+    if (tid < N) {
+      float s = 0.0f;
+      for (int q = 0; q < G; ++q) s += part[q * NP + tid];
+      out[tid] = expf(-gamma * s);
+    }
+  }
+  __syncthreads();
+}
+
+// out[k] = -sum_n e[n] (x[k] - wT[n][k]) for k < Kin, wT (N, Kin) row-major: the transposed means (e, x, out, part: LDS; out
+// is neither e nor x).  A thread per k reads wT coalesced; the split and the order of the sums are pilco_gemv's.  Ends with
+// a barrier.
+__device__ __forceinline__ void pilco_rbf_dx(const float *__restrict__ wT, int N, int Kin, const float *e, const float *x,
+                                             float *out, float *part) {
+  const int tid = threadIdx.x;
+  if (Kin > PILCO_THREADS / 2) {
+    for (int c0 = 0; c0 < Kin; c0 += PILCO_THREADS) {
+      const int k = min(c0 + tid, Kin - 1);
+      const float *col = wT + k;
+      const float xk = x[k];
+      float acc = 0.0f;
+#pragma unroll 16
+      for (int n = 0; n < N; ++n) acc = fmaf(e[n], xk - col[(long long)n * Kin], acc);
+      if (c0 + tid < Kin) out[c0 + tid] = -acc;
+    }
+  } else {
+    int KP = 1;
+    while (KP < Kin) KP <<= 1;
+    const int G = PILCO_THREADS / KP, gi = tid / KP, k = min(tid % KP, Kin - 1);
+    const int len = (N + G - 1) / G;
+    const int n0 = min(gi * len, N), n1 = min(n0 + len, N);
+    const float *col = wT + k;
+    const float xk = x[k];
+    float acc = 0.0f;
+#pragma unroll 16
+    for (int n = n0; n < n1; ++n) acc = fmaf(e[n], xk - col[(long long)n * Kin], acc);
+    part[tid] = acc;                                  // tid = gi * KP + (tid % KP)
+    __syncthreads();
+    if (tid < Kin) {
+      float s = 0.0f;
+      for (int q = 0; q < G; ++q) s += part[q * KP + tid];
+      out[tid] = -s;
+    }
+  }
+  __syncthreads();
+}
+
 // s_u,i (u = 0..H) into sout[0 .. S) (LDS) and st, its reward into rew; u >= 1: m_u and sd_u from the staged y_u, which
 // workgroup 0 also leaves in msd.  Ends with a barrier.
 __device__ __forceinline__ void pilco_state(const PilcoArgs &g, int u, float *yl, float *sout) {
@@ -189,6 +281,48 @@ __device__ __forceinline__ void pilco_state(const PilcoArgs &g, int u, float *yl
   }
   __syncthreads();
   if (tid == 0) g.rew[(long long)u * K + i] = pilco_reward(g.reward, sout, (float)u);
+}
+
+// The policy: xin[0 .. S) -> xin[S .. S + A) (LDS) and arow[0 .. A); TAPE: the hidden activations, in layer order, to
+// tape[0 .. tw_pol).  Ends with a barrier.
+template <bool TAPE>
+__device__ __forceinline__ void pilco_policy(const PilcoArgs &g, float *xin, float *bufA, float *bufB, float *part, float *tape,
+                                             float *arow) {
+  const int tid = threadIdx.x, S = g.S;
+  const float *in = xin;
+  float *out = bufA;
+  for (int l = 0; l < g.pol.L; ++l) {
+    const int Kin = g.pol.dims[l], N = g.pol.dims[l + 1], act = g.pol.acts[l];
+    const float *w = g.phi + g.pol.w_off[l];
+    if (g.pol.kind[l] == PYZ_PILCO_RBF) pilco_rbf(w, g.pol.gamma[l], Kin, N, in, out, part);     // (uniform)
+    else pilco_gemv(w, w + Kin * N, Kin, N, in, out, part);
+    if (l + 1 < g.pol.L) {
+      for (int n = tid; n < N; n += PILCO_THREADS) {
+        const float h = pyz_act(out[n], act);
+        out[n] = h;
+        if (TAPE) tape[n] = h;
+      }
+      if (TAPE) tape += N;
+      in = out;
+      out = out == bufA ? bufB : bufA;
+    } else {
+      if (tid < N) {
+        float a;
+        if (act == PYZ_ACT_SOFTMAX) {
+          float mx = out[0];
+          for (int k = 1; k < N; ++k) mx = fmaxf(mx, out[k]);
+          float se = 0.0f;
+          for (int k = 0; k < N; ++k) se += expf(out[k] - mx);
+          a = expf(out[tid] - mx) / se;
+        } else {
+          a = pyz_act(out[tid], act);
+        }
+        xin[S + tid] = a;
+        arow[tid] = a;
+      }
+    }
+    __syncthreads();
+  }
 }
 
 // grid (x, K + 2): rows y < K transpose draw y's kernels, row K the policy's, row K + 1 writes the scalars and c_t
@@ -244,41 +378,8 @@ __global__ void __launch_bounds__(PILCO_THREADS) k_pilco_fwd(PilcoArgs g) {
   pilco_state(g, t - 1, yl, xin);
 
   float *tape = g.tape + ((long long)(t - 1) * K + i) * g.tw;
-  // the policy: xin[0 .. S) -> xin[S .. S + A)
-  {
-    const float *in = xin;
-    float *out = bufA;
-    for (int l = 0; l < g.pol.L; ++l) {
-      const int Kin = g.pol.dims[l], N = g.pol.dims[l + 1], act = g.pol.acts[l];
-      pilco_gemv(g.phi + g.pol.w_off[l], g.phi + g.pol.w_off[l] + Kin * N, Kin, N, in, out, part);
-      if (l + 1 < g.pol.L) {
-        for (int n = tid; n < N; n += PILCO_THREADS) {
-          const float h = pyz_act(out[n], act);
-          out[n] = h;
-          tape[n] = h;
-        }
-        tape += N;
-        in = out;
-        out = out == bufA ? bufB : bufA;
-      } else {
-        if (tid < N) {
-          float a;
-          if (act == PYZ_ACT_SOFTMAX) {
-            float mx = out[0];
-            for (int k = 1; k < N; ++k) mx = fmaxf(mx, out[k]);
-            float se = 0.0f;
-            for (int k = 0; k < N; ++k) se += expf(out[k] - mx);
-            a = expf(out[tid] - mx) / se;
-          } else {
-            a = pyz_act(out[tid], act);
-          }
-          xin[S + tid] = a;
-          g.ac[((long long)(t - 1) * K + i) * A + tid] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  pilco_policy<true>(g, xin, bufA, bufB, part, tape, g.ac + ((long long)(t - 1) * K + i) * A);
+  tape += g.tw_pol;
   // this particle's draw of the dynamics: xin[0 .. S + A) -> y_t,i
   {
     const float *wd = g.W + (long long)i * g.Dd;
@@ -302,6 +403,18 @@ __global__ void __launch_bounds__(PILCO_THREADS) k_pilco_fwd(PilcoArgs g) {
       }
     }
   }
+}
+
+// grid (rows): workgroup i is the policy of k_pilco_fwd on row i of states (rows, S), into row i of actions (rows, A)
+__global__ void __launch_bounds__(PILCO_THREADS) k_pilco_act(PilcoArgs g, const float *__restrict__ states, float *actions) {
+  extern __shared__ __attribute__((aligned(16))) float pilco_lds[];
+  const int tid = threadIdx.x, S = g.S;
+  const long long i = blockIdx.x;
+  float *xin = pilco_lds, *bufA = xin + PILCO_MAX_IN, *bufB = bufA + g.maxw, *part = bufB + g.maxw;
+  const float s = states[i * S + min(tid, S - 1)];
+  if (tid < S) xin[tid] = s;
+  __syncthreads();
+  pilco_policy<false>(g, xin, bufA, bufB, part, nullptr, actions + i * g.A);
 }
 
 __global__ void __launch_bounds__(PILCO_THREADS) k_pilco_tail(PilcoArgs g) {
@@ -397,15 +510,30 @@ __global__ void __launch_bounds__(PILCO_THREADS) k_pilco_bwd(PilcoArgs g) {
       const int Kin = g.pol.dims[l], N = g.pol.dims[l + 1];
       in -= Kin;
       float *pw = prow + g.pol.w_off[l];
-      const int nw = (Kin + 1) * N;               // kernel, then bias (input 1)
-      for (int e = tid; e < nw; e += PILCO_THREADS) {
-        const int k = e / N, n = e - k * N;
-        const float x = k < Kin ? in[k] : 1.0f;
-        const float old = first ? 0.0f : pw[e];
-        pw[e] = fmaf(x, delta[n], old);
+      if (g.pol.kind[l] == PYZ_PILCO_RBF) {         // (uniform)
+        const float *h = in + Kin, *mean = g.phi + g.pol.w_off[l];   // the layer's output follows its input in pact
+        const float g2 = 2.0f * g.pol.gamma[l];
+        for (int n = tid; n < N; n += PILCO_THREADS) delta[n] = g2 * delta[n] * h[n];          // delta -> e
+        __syncthreads();
+        const int nw = Kin * N;                     // the means: no bias row
+        for (int e = tid; e < nw; e += PILCO_THREADS) {
+          const int k = e / N, n = e - k * N;
+          const float d = in[k] - mean[e];
+          const float old = first ? 0.0f : pw[e];
+          pw[e] = fmaf(delta[n], d, old);
+        }
+        pilco_rbf_dx(g.phiT + g.pol.w_off[l], N, Kin, delta, in, other, part);
+      } else {
+        const int nw = (Kin + 1) * N;               // kernel, then bias (input 1)
+        for (int e = tid; e < nw; e += PILCO_THREADS) {
+          const int k = e / N, n = e - k * N;
+          const float x = k < Kin ? in[k] : 1.0f;
+          const float old = first ? 0.0f : pw[e];
+          pw[e] = fmaf(x, delta[n], old);
+        }
+        pilco_gemv(g.phiT + g.pol.w_off[l], nullptr, N, Kin, delta, other, part);
       }
-      pilco_gemv(g.phiT + g.pol.w_off[l], nullptr, N, Kin, delta, other, part);
-      if (l > 0) {
+      if (l > 0 && g.pol.kind[l - 1] == PYZ_PILCO_DENSE) {     // an RBF layer's h factor is taken in its own step
         const int act = g.pol.acts[l - 1];
         for (int k = tid; k < Kin; k += PILCO_THREADS) other[k] *= pyz_act_grad(in[k], act);
         __syncthreads();

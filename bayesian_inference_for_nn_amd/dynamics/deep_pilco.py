@@ -4,7 +4,8 @@ that BNN.  The rollout, its gradient and the policy's Adam step are one chain of
 csrc/pyz_pilco.h); everything here is plumbing around it.
 
 Network templates are a compat ``tensorflow.keras.Sequential`` of hidden ``Dense`` layers, or a list of
-``(units, activation)`` pairs; the input and the output layer are added from the environment's spaces."""
+``(units, activation)`` pairs; the input and the output layer are added from the environment's spaces.  A policy template
+may also hold ``RBF(units, gamma)`` layers (the reference's policy: ``Sequential([RBF(80, 0.5)])``)."""
 
 from __future__ import annotations
 
@@ -13,41 +14,60 @@ import json
 import numpy as np
 
 from ..datasets import Dataset
-from ..nn.model import model_from_json, sequential_json
+from ..nn.model import PolicyNet, model_from_json, sequential_json
 from .control import Control, Policy
 from .rewards import MIN_STATE, all_rewards
 
 DEFAULT_RANDOM_EPOCHS = 5
 
 
+class RBF:
+    """The radial-basis hidden layer of a policy template (deep_pilco.py:28-51): h[n] = exp(-gamma * sum_k (x[k] -
+    mean[k][n])^2) with one trainable variable `mean` (in, units), drawn uniform in [-0.05, 0.05), and no bias.  gamma is a
+    constant of the layer.  It holds its two arguments; the network is built by complete_model."""
+
+    def __init__(self, units, gamma, **kwargs):
+        self.units, self.gamma = int(units), float(gamma)
+
+    def __repr__(self):
+        return f"RBF({self.units}, {self.gamma})"
+
+
 def template_layers(template):
-    """[(units, activation name)] of a template's hidden layers."""
+    """A template's hidden layers: (units, activation name) of a Dense layer, the RBF object of an RBF layer."""
     if template is None:
         return []
     if isinstance(template, (list, tuple)):
-        return [(int(u), str(a)) for u, a in template]
+        return [l if isinstance(l, RBF) else (int(l[0]), str(l[1])) for l in template]
     layers = getattr(template, "_layers", None)
     if layers is None:
         layers = template.layers
     out = []
     for layer in layers:
+        if isinstance(layer, RBF):
+            out.append(layer)
+            continue
         if not hasattr(layer, "units"):
-            raise ValueError("a network template holds Dense layers only")
+            raise ValueError("a network template holds Dense and RBF layers only")
         out.append((int(layer.units), str(getattr(layer, "activation", None) or "linear")))
     return out
 
 
 def complete_model(template, ipd, opd, out_activation):
-    """The DenseNet input ipd -> the template's hidden layers -> Dense(opd[0], out_activation)."""
+    """The DenseNet input ipd -> the template's hidden layers -> Dense(opd[0], out_activation); with an RBF layer among
+    them, the PolicyNet of the same shape."""
     hidden = template_layers(template)
+    if any(isinstance(l, RBF) for l in hidden):
+        layers = [("rbf", l.units, l.gamma) if isinstance(l, RBF) else ("dense", l[0], l[1]) for l in hidden]
+        return PolicyNet(int(np.prod(ipd)), layers, int(opd[0]), out_activation)
     units = [u for u, _ in hidden] + [int(opd[0])]
     acts = [a for _, a in hidden] + [out_activation]
     return model_from_json(sequential_json(tuple(int(d) for d in ipd), units, acts))
 
 
 class NNPolicy(Policy):
-    """A Dense policy network; hyperparams may carry ``lr`` (default 1e-3) for its Adam optimizer.  The parameters, the
-    two Adam moments and the step count live on the device; ``network`` holds a host copy for ``act``."""
+    """A policy network of Dense and RBF hidden layers; hyperparams may carry ``lr`` (default 1e-3) for its Adam optimizer.
+    The parameters, the two Adam moments and the step count live on the device; ``network`` holds a host copy for ``act``."""
 
     def __init__(self, network, hyperparams):
         super().__init__()
@@ -114,6 +134,8 @@ class DynamicsTraining:
     def _create_model(self, ipd, opd):
         if self.model_ready:
             return
+        if any(isinstance(l, RBF) for l in template_layers(self.template)):
+            raise ValueError("an RBF layer belongs to a policy template: the dynamics model is a Dense network")
         self.model = complete_model(self.template, ipd, opd, out_activation="linear")
 
     def compile_more(self, extra):
@@ -193,7 +215,8 @@ class BayesianDynamics(Control):
         K, S = int(self.kp), self.state_fd[0]
         bnn = self.dyn_training.optimizer.result()
         if self._plan is None:
-            self._plan = engine.PilcoPlan(self.policy.network.spec, bnn._model.spec, K, self.horizon)
+            net = self.policy.network
+            self._plan = engine.PilcoPlan(net if isinstance(net, PolicyNet) else net.spec, bnn._model.spec, K, self.horizon)
             f32 = dict(dtype=torch.float32, device="cuda")
             self._bufs = (torch.empty((K, self._plan.D_dyn), **f32), torch.empty((K, S), **f32),
                           torch.empty((self.horizon, K, S), **f32))
@@ -222,7 +245,7 @@ class BayesianDynamics(Control):
                 f.write(str([str(a) + "," for a in actions[t - 1]]))
             f.write("\nTotal cost: " + str(float(cost.item())) + "\n")
             f.write("Gradient sample: " + str(grad[-n_last:].cpu().numpy()) + ", length " +
-                    str(2 * len(self.policy.network.acts)) + "\n")
+                    str(len(self.policy.network.trainable_variables)) + "\n")
         return False
 
     def learn(self, nb_epochs, record_file, random_ep):

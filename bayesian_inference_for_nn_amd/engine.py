@@ -772,12 +772,14 @@ class MLPPlan:
 
 class PilcoPlan:
     """Owns one `pyz_pilco` handle: the policy update of Deep-PILCO (dynamics/deep_pilco.py:247-326) for a policy net
-    `policy_spec` (dims (S, hidden..., A)) and `particles` draws of a dynamics net `dynamics_spec` (dims (S + A, hidden...,
-    S), last layer linear), with the tape of up to max_horizon steps.  The specs' `loss` is not used.  cost and grad live
+    `policy_spec` (dims (S, hidden..., A): a Dense-only MLPSpec, or a description with `dims`, `acts`, `n_params` and
+    per-layer `kinds` ("dense" | "rbf") and `gammas`, such as nn.model.PolicyNet) and `particles` draws of a dynamics net
+    `dynamics_spec` (dims (S + A, hidden..., S), last layer linear), with the tape of up to max_horizon steps.  The specs'
+    `loss` is not used.  cost and grad live
     in buffers of the plan (so do states and actions unless the caller passes its own): a captured graph is replayed
     while the caller's tensors stay where they are, and the returned tensors are overwritten by the next call."""
 
-    def __init__(self, policy_spec: MLPSpec, dynamics_spec: MLPSpec, particles: int, max_horizon: int, device=None):
+    def __init__(self, policy_spec, dynamics_spec: MLPSpec, particles: int, max_horizon: int, device=None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("bayesian_inference_for_nn_amd needs an MI355X (no HIP device visible); there is no CPU path")
@@ -786,19 +788,30 @@ class PilcoPlan:
         self.K, self.max_horizon = int(particles), int(max_horizon)
         self.S, self.A = int(policy_spec.dims[0]), int(policy_spec.dims[-1])
         self.D_pol, self.D_dyn = policy_spec.n_params, dynamics_spec.n_params
-        pd = (C.c_int32 * len(policy_spec.dims))(*policy_spec.dims)
-        pa = (C.c_int32 * len(policy_spec.acts))(*[ACT[a] for a in policy_spec.acts])
-        dd = (C.c_int32 * len(dynamics_spec.dims))(*dynamics_spec.dims)
-        da = (C.c_int32 * len(dynamics_spec.acts))(*[ACT[a] for a in dynamics_spec.acts])
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            check(self.lib.pyz_pilco_create(policy_spec.n_layers, pd, pa, dynamics_spec.n_layers, dd, da, self.K,
-                                            self.max_horizon, C.byref(h)))
+            check(self._create(self.lib, policy_spec, dynamics_spec, self.K, self.max_horizon, h))
         self.h = h
         f32 = dict(dtype=torch.float32, device=self.device)
         self._cost, self._grad = torch.zeros(1, **f32), torch.zeros(self.D_pol, **f32)
         self._states = torch.zeros((self.max_horizon + 1, self.K, self.S), **f32)
         self._actions = torch.zeros((self.max_horizon, self.K, self.A), **f32)
+
+    @staticmethod
+    def _create(lib, policy_spec, dynamics_spec, particles, max_horizon, h):
+        """The return code of pyz_pilco_create (a Dense-only MLPSpec) or pyz_pilco_create_layers (a policy description
+        with per-layer `kinds` and `gammas`: nn.model.PolicyNet)."""
+        n = len(policy_spec.acts)
+        pd = (C.c_int32 * (n + 1))(*policy_spec.dims)
+        pa = (C.c_int32 * n)(*[ACT[a] for a in policy_spec.acts])
+        dd = (C.c_int32 * len(dynamics_spec.dims))(*dynamics_spec.dims)
+        da = (C.c_int32 * len(dynamics_spec.acts))(*[ACT[a] for a in dynamics_spec.acts])
+        kinds = getattr(policy_spec, "kinds", None)
+        if kinds is None:
+            return lib.pyz_pilco_create(n, pd, pa, dynamics_spec.n_layers, dd, da, particles, max_horizon, C.byref(h))
+        pk = (C.c_int32 * n)(*[_lib.PILCO_KIND[k] for k in kinds])
+        pg = (C.c_float * n)(*policy_spec.gammas)
+        return lib.pyz_pilco_create_layers(n, pd, pa, pk, pg, dynamics_spec.n_layers, dd, da, particles, max_horizon, C.byref(h))
 
     def close(self):
         if getattr(self, "h", None):
@@ -864,6 +877,17 @@ class PilcoPlan:
                                              ptr(self._cost), ptr(self._grad), ptr(states), ptr(actions),
                                              1 if use_graph else 0, _stream()))
         return self._cost, self._grad, states[:H + 1], actions[:H]
+
+    def act(self, phi, states):
+        """actions (N, A): the policy's outputs under phi (D_pol,) for states (N, S), N >= 1, in one launch of the rollout's
+        own policy forward -- for the states of a rollout they are the rollout's actions bit for bit."""
+        _f32(phi, (self.D_pol,), "phi")
+        _f32(states, name="states")
+        if states.dim() != 2 or states.shape[1] != self.S or states.shape[0] < 1:
+            raise ValueError(f"states has shape {tuple(states.shape)}, expected (N >= 1, {self.S})")
+        actions = torch.empty((states.shape[0], self.A), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_pilco_act(self.h, ptr(phi), ptr(states), int(states.shape[0]), ptr(actions), _stream()))
+        return actions
 
 
 class KernelProbe:

@@ -162,7 +162,107 @@ class DenseNet:
         return np.asarray(self._forward(x))
 
 
+class PolicyNet:
+    """A Deep-PILCO policy network with at least one RBF hidden layer (Pyesian/dynamics/deep_pilco.py:28-51):
+    h[n] = exp(-gamma * sum_k (x[k] - mean[k][n])^2), one trainable variable `mean` (in, units), no bias.
+
+    ``hidden``: per hidden layer ``("rbf", units, gamma)`` or ``("dense", units, activation)``; a Dense output layer of
+    ``out_units`` follows.  The flat vector keeps the layers in network order: an RBF layer's means row-major (in, units),
+    a Dense layer's kernel (in, out) then its bias.  Initial weights are Keras': means uniform in [-0.05, 0.05)
+    (``'uniform'``), Dense kernels Glorot, biases zero.
+
+    This is what NNPolicy, BayesianDynamics and engine.PilcoPlan use of a network, nothing more: it is not an MLPSpec, no
+    optimizer or BayesianModel takes it, and it has no Keras config (the reference's layer has no ``get_config`` either).
+    ``__call__`` is the policy forward of the rollout kernels (pyz_pilco_act)."""
+
+    def __init__(self, in_dim: int, hidden: Sequence[tuple], out_units: int, out_activation: str, rng=None):
+        dims, acts, kinds, gammas = [int(in_dim)], [], [], []
+        for kind, units, arg in hidden:
+            if kind == "rbf":
+                gamma = float(arg)
+                if not (np.isfinite(gamma) and gamma > 0):
+                    raise ValueError(f"RBF gamma must be a finite number > 0, not {arg!r}")
+                acts.append("linear")
+                gammas.append(gamma)
+            elif kind == "dense":
+                acts.append(_activation_name(arg))
+                gammas.append(0.0)
+            else:
+                raise ValueError(f"unknown layer kind {kind!r}")
+            kinds.append(kind)
+            dims.append(int(units))
+        dims.append(int(out_units))
+        acts.append(_activation_name(out_activation))
+        kinds.append("dense")
+        gammas.append(0.0)
+        if "rbf" not in kinds:
+            raise ValueError("a network of Dense layers only is a DenseNet")
+        if min(dims) < 1:
+            raise ValueError(f"layer widths must be >= 1: {dims}")
+        self.dims, self.acts, self.kinds, self.gammas = tuple(dims), tuple(acts), tuple(kinds), tuple(gammas)
+        self.weights_flat = np.zeros(self.n_params, dtype=np.float32)
+        self._plan = None
+        self.reset_keras(rng if rng is not None else np.random.default_rng())
+
+    def layer_slices(self) -> List[slice]:
+        out, off = [], 0
+        for i, o, kind in zip(self.dims[:-1], self.dims[1:], self.kinds):
+            n = i * o if kind == "rbf" else (i + 1) * o
+            out.append(slice(off, off + n))
+            off += n
+        return out
+
+    @property
+    def n_params(self) -> int:
+        return self.layer_slices()[-1].stop
+
+    # ------------------------------------------------------------------ weights
+    def reset_keras(self, rng: np.random.Generator):
+        for sl, i, o, kind in zip(self.layer_slices(), self.dims[:-1], self.dims[1:], self.kinds):
+            if kind == "rbf":
+                self.weights_flat[sl] = rng.uniform(-0.05, 0.05, size=i * o).astype(np.float32)
+            else:
+                lim = np.sqrt(6.0 / (i + o))
+                self.weights_flat[sl.start:sl.start + i * o] = rng.uniform(-lim, lim, size=i * o).astype(np.float32)
+                self.weights_flat[sl.start + i * o:sl.stop] = 0.0
+
+    @property
+    def trainable_variables(self) -> List[np.ndarray]:
+        """Views of the flat vector: [mean (in, units)] of an RBF layer, [kernel (in, out), bias (out)] of a Dense one."""
+        out = []
+        for sl, i, o, kind in zip(self.layer_slices(), self.dims[:-1], self.dims[1:], self.kinds):
+            flat = self.weights_flat[sl]
+            out.append(flat[: i * o].reshape(i, o))
+            if kind == "dense":
+                out.append(flat[i * o:])
+        return out
+
+    get_weights = DenseNet.get_weights
+    set_weights = DenseNet.set_weights
+    set_flat = DenseNet.set_flat
+
+    def to_json(self) -> str:
+        raise ValueError("a network with an RBF layer has no Keras config: the RBF layer defines no get_config")
+
+    # ------------------------------------------------------------------ inference
+    def _forward(self, x) -> np.ndarray:
+        import torch
+        from ..engine import MLPSpec, PilcoPlan
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
+        if self._plan is None:      # the policy alone: the smallest dynamics net, particle count and horizon a plan takes
+            S, A = self.dims[0], self.dims[-1]
+            self._plan = PilcoPlan(self, MLPSpec((S + A, S), ("linear",), "mse"), 2, 1)
+        out = self._plan.act(torch.as_tensor(self.weights_flat).cuda(), torch.as_tensor(x).cuda())
+        return out.cpu().numpy()
+
+    def __call__(self, x, training=False):
+        return Array(self._forward(x))
+
+
 def model_from_json(model_config: str) -> DenseNet:
+    if isinstance(model_config, PolicyNet):
+        raise ValueError("a network with an RBF layer is a Deep-PILCO policy only: no optimizer, DynamicsTraining or "
+                         "BayesianModel takes it")
     return DenseNet(model_config)
 
 

@@ -54,6 +54,9 @@ class Optimizer(ABC):
         pass
 
     def compile(self, hyperparameters, model_config: str, dataset, verbose=True, **kwargs):
+        if hasattr(model_config, "kinds"):
+            raise ValueError("a network with an RBF layer is a Deep-PILCO policy only: an optimizer takes a Keras Sequential "
+                             "JSON of Dense layers")
         if self.__compiled:
             raise Exception("Model Already compiled")
         else:

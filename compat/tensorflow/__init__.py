@@ -69,6 +69,9 @@ class Sequential:
                 elif isinstance(l, Dense):
                     units.append(l.units)
                     acts.append(l.activation)
+                elif not isinstance(l, InputLayer):      # an RBF layer of a Deep-PILCO policy template: kept by add()
+                    raise ValueError(f"{type(l).__name__} has no Keras config: a Sequential holding it is a policy "
+                                     "template for NNPolicy, not a model")
             if shape is None:
                 raise ValueError("the first layer needs input_shape")
             self._net = _model_from_json(_sequential_json(shape, units, acts, flatten=flatten))

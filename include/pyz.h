@@ -588,7 +588,7 @@ int pyz_score_rows(const float *d_mean, int groups, int64_t n, int C, const void
  *   PYZ_REWARD_ACB   r = 4 - 3 s0 - (s0 s2 - s1 s3) + s4^2              S >= 5
  * pyz_pilco_create refuses (PYZ_E_INVALID, no device touched) K < 2 (sd is identically 0 and the gradient NaN), a
  * dynamics net whose last layer is not linear or whose dims do not fit the policy's, and anything past the limits
- * K <= 256, S + A <= 64, layer widths <= 512, at most 8 Dense layers per net, max_horizon <= 4096.  The handle owns the
+ * K <= 256, S + A <= 64, layer widths <= 512, at most 8 layers per net, max_horizon <= 4096.  The handle owns the
  * tape of max_horizon steps (pyz_pilco_workspace_bytes).
  * pyz_pilco_policy_step: d_phi float32[D_pol]; d_W (K, D_dyn); d_s0 (K, S); d_eps (H, K, S) unit normals (the kernels draw
  * nothing: fill it with pyz_fill_normal, stream PYZ_STREAM_PILCO = 8 of csrc/pyz_rng.h); gamma the discount.  adam_t = 0: gradient only, d_phi
@@ -598,18 +598,34 @@ int pyz_score_rows(const float *d_mean, int groups, int64_t n, int C, const void
  * bits are the same on every call.  use_graph != 0: the 2 H + 2 launches behind the first are captured once per (H, freq,
  * reward and every pointer argument) as one chain on `stream` and replayed.  PYZ_E_INVALID for a reward whose indices
  * exceed S or an unknown one, freq < 1, a null pointer; PYZ_E_SHAPE for H outside [1, max_horizon].  Nothing is launched
- * after a refusal. */
+ * after a refusal.
+ * pyz_pilco_create_layers is pyz_pilco_create with a kind and a gamma per policy layer (pyz_pilco_create: every layer
+ * PYZ_PILCO_DENSE).  PYZ_PILCO_RBF is the RBF layer of deep_pilco.py:28-51, h[n] = exp(-gamma sum_k (x[k] - mean[k][n])^2):
+ * its one variable `mean` (in, units) row-major takes in * units floats of phi at the layer's place, there is no bias, its
+ * activation entry must be PYZ_ACT_LINEAR and gamma is a constant of the plan, not part of phi.  Refused (PYZ_E_INVALID, no
+ * device touched): an unknown kind, an RBF as the last policy layer, a gamma that is not finite or not > 0, RBF units
+ * outside [1, 512].  The dynamics net stays a Dense stack.
+ * pyz_pilco_act: d_actions (N, A) = the policy of the plan on d_states (N, S) under d_phi, one launch, the arithmetic of
+ * the rollout (its actions for a rollout's states are the rollout's actions bit for bit).  PYZ_E_INVALID for N < 1 or a
+ * null pointer, before any launch. */
 #define PYZ_REWARD_CART 0
 #define PYZ_REWARD_ACB 1
+#define PYZ_PILCO_DENSE 0
+#define PYZ_PILCO_RBF 1
 typedef struct pyz_pilco pyz_pilco;
 int pyz_pilco_create(int n_policy_layers, const int32_t *h_policy_dims, const int32_t *h_policy_acts, int n_dynamics_layers,
                      const int32_t *h_dynamics_dims, const int32_t *h_dynamics_acts, int particles, int max_horizon,
                      pyz_pilco **out);
+int pyz_pilco_create_layers(int n_policy_layers, const int32_t *h_policy_dims, const int32_t *h_policy_acts,
+                            const int32_t *h_policy_kinds, const float *h_policy_gammas, int n_dynamics_layers,
+                            const int32_t *h_dynamics_dims, const int32_t *h_dynamics_acts, int particles, int max_horizon,
+                            pyz_pilco **out);
 int pyz_pilco_destroy(pyz_pilco *plan);
 int64_t pyz_pilco_workspace_bytes(const pyz_pilco *plan);
 int pyz_pilco_policy_step(pyz_pilco *plan, float *d_phi, float *d_m, float *d_v, int64_t adam_t, const float *d_W,
                           const float *d_s0, const float *d_eps, int H, int freq, float gamma, int reward, float lr,
                           float *d_cost, float *d_grad, float *d_states, float *d_actions, int use_graph, void *stream);
+int pyz_pilco_act(pyz_pilco *plan, const float *d_phi, const float *d_states, int N, float *d_actions, void *stream);
 
 /* ---- noise: d_out[i] = mean + std * z_i, z from Philox stream (seed, stream, step).
  * (tf.random.normal at SGLD.py:67, HMC.py:171; tfp samplers at BBB.py:234-237,

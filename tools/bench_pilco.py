@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Cost of one Deep-PILCO policy update (GPU box): PilcoPlan.policy_step, Adam on, on seeded inputs of a case of
-tests/pilco_checks.py (default `example`: K = 32, H = 32, policy 6 -> 80 -> 3, dynamics 9 -> 512 -> 256 -> 6).
+tests/pilco_checks.py (default `example`: K = 32, H = 32, policy 6 -> 80 -> 3, dynamics 9 -> 512 -> 256 -> 6) or of
+tests/pilco_rbf_checks.py (`rbf_example`: the same shape with the policy's hidden layer RBF(80, 0.5)).
     graph_ms / plain_ms   ms per update through the captured graph and through plain launches: --updates updates after
                           --warmup ones, host clock around calls that end in a stream synchronise, --rounds rounds per path,
                           the two paths alternating in one process
@@ -22,21 +23,28 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 import pilco_checks as pc  # noqa: E402
+import pilco_rbf_checks as rc  # noqa: E402
 from bayesian_inference_for_nn_amd.engine import KernelProbe, MLPSpec, PilcoPlan  # noqa: E402
+from bayesian_inference_for_nn_amd.nn.model import PolicyNet  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", default="example", choices=[c.name for c in pc.CASES])
+    ap.add_argument("--case", default="example", choices=[c.name for c in pc.CASES + rc.CASES])
     ap.add_argument("--updates", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_pilco needs the GPU: a CPU run says nothing about it")
-    case = pc.CASE[a.case]
-    d = {k: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32)).cuda() for k, v in pc.make_inputs(case).items()}
-    plan = PilcoPlan(MLPSpec(case.pol_dims, case.pol_acts, "mse"), MLPSpec(case.dyn_dims, case.dyn_acts, "mse"), case.K, case.H)
+    if a.case in rc.CASE:
+        case = rc.CASE[a.case]
+        inputs, policy = rc.make_inputs(case), PolicyNet(case.S, case.pol_hidden, case.A, case.pol_out)
+    else:
+        case = pc.CASE[a.case]
+        inputs, policy = pc.make_inputs(case), MLPSpec(case.pol_dims, case.pol_acts, "mse")
+    d = {k: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32)).cuda() for k, v in inputs.items()}
+    plan = PilcoPlan(policy, MLPSpec(case.dyn_dims, case.dyn_acts, "mse"), case.K, case.H)
     phi, m, v = d["phi"].clone(), torch.zeros_like(d["phi"]), torch.zeros_like(d["phi"])
 
     def update(t, use_graph):
@@ -59,6 +67,7 @@ def main():
         with KernelProbe(4 * case.H + 16) as kp:
             update(a.warmup + 1, False)
     out = {"tool": "bench_pilco", "case": case.name, "K": case.K, "H": case.H, "policy": list(case.pol_dims),
+           "policy_kinds": list(getattr(case, "pol_kinds", ("dense",) * len(case.pol_acts))),
            "dynamics": list(case.dyn_dims), "updates": a.updates, "warmup": a.warmup,
            "graph_ms": float(np.median(ms[True])), "plain_ms": float(np.median(ms[False])),
            "ms_rounds": {"graph": ms[True], "plain": ms[False]},
