@@ -29,9 +29,21 @@ namespace {
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+void drop_graphs(pyz_mlp *m);
+
+// Grows a lazily sized buffer of the plan.  A buffer that MOVES takes every captured graph of the plan with it: the graphs
+// bake in the plan's pointers (m->grad in the unfused chained SGLD step, grad2, part2, hm_buf, ...), and a replay would read
+// and write what was just freed.  The keys of the caches still mix the pointers they know of; dropping here covers the ones
+// they do not, for every buffer that goes through this function.  Growth is rare (a call with more particles than any
+// before it) and never happens inside a capture: every run sizes its buffers before it captures.  The first allocation
+// (nothing to move) drops nothing.
 int ensure_bytes(void **ptr, size_t *cap, size_t need, pyz_mlp *m) {
   if (*cap >= need) return PYZ_OK;
-  if (*ptr) PYZ_HIP(hipFree(*ptr));
+  if (*ptr) {
+    PYZ_HIP(hipDeviceSynchronize());   // a graph launched on any stream may still use the buffer, and is destroyed below
+    PYZ_HIP(hipFree(*ptr));
+    drop_graphs(m);
+  }
   *ptr = nullptr;
   *cap = 0;
   PYZ_HIP(hipMalloc(ptr, need));
@@ -101,6 +113,13 @@ struct pyz_mlp_full : pyz_mlp {
 namespace {
 
 inline pyz_mlp_full *full(pyz_mlp *m) { return static_cast<pyz_mlp_full *>(m); }
+
+void drop_graphs(pyz_mlp *m) {
+  m->graphs.drop();
+  full(m)->x.hm_graphs.drop();
+  full(m)->x.hmc_run_graphs.drop();
+  full(m)->x.adam_graphs.drop();
+}
 
 int need_grad(pyz_mlp *m, int P) {
   m->grad_owner = 2;   // (pyz_svgd_gradients sets 1 after this call)
@@ -1497,6 +1516,7 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
 
   int s = 0;
   m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  m->graphs.begin_call();   // (an eager call captures nothing: pyz_sgld_run_info)
   // A run of ANY length is replayed from captured graphs: chunks of G steps (slot 0) and ONE graph for the
   // remainder, captured for its exact length and kept (the other slots, least recently used one replaced) -- a
   // caller that repeats its run lengths (train(n) again, bench.py's warm-up / timed pair) pays one capture per
@@ -1525,7 +1545,6 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
       mix((unsigned long long)(uintptr_t)bbb->w2); mix((unsigned long long)(uintptr_t)bbb->rho); mix((unsigned long long)(uintptr_t)full(m)->x.part2);
     }
     m->graphs.rekey(key);
-    m->graphs.begin_call();
     while (s < n_steps) {
       const int len = std::min(G, n_steps - s);
       const bool rest = len < G;   // the remainder: its own graph, by exact length in slots 1 ..; slot 0 holds the full chunk
@@ -3548,6 +3567,12 @@ int pyz_last_run_info(const pyz_mlp *m, int32_t *h_graph_steps, int32_t *h_eager
   if (h_graph_steps) *h_graph_steps = m->run_graph_steps;
   if (h_eager_steps) *h_eager_steps = m->run_eager_steps;
   if (h_graph_launches) *h_graph_launches = m->run_graph_launches;
+  return PYZ_OK;
+}
+
+int pyz_sgld_run_info(const pyz_mlp *m, int32_t *h_captures) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (h_captures) *h_captures = m->graphs.captures;
   return PYZ_OK;
 }
 

@@ -391,6 +391,13 @@ class MLPPlan:
         check(self.lib.pyz_last_run_info(self.h, None, None, C.byref(n)))
         return n.value
 
+    def sgld_run_captures(self) -> int:
+        """Graphs the last sgd_run / swag_run / sgld_run / bbb_run call on this plan had to capture (0: every chunk was
+        replayed from the cache, or launched eagerly)."""
+        n = C.c_int32()
+        check(self.lib.pyz_sgld_run_info(self.h, C.byref(n)))
+        return n.value
+
     def check_finite(self):
         """Synchronises the current stream; raises PyzError (code E_NAN) if a step since the last check produced a
         NaN / Inf loss."""

@@ -245,6 +245,13 @@ int pyz_swag_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, 
 int pyz_last_run_info(const pyz_mlp *mlp, int32_t *h_graph_steps, int32_t *h_eager_steps,
                       int32_t *h_graph_launches);
 
+/* *h_captures = the graphs the last pyz_sgd_run / pyz_swag_run / pyz_sgld_run / pyz_bbb_run call on this plan had to
+ * capture (0: every chunk was replayed from the cache, or launched eagerly).  The cache holds the graphs of one set of
+ * arguments (the caller's pointers, the seed, the largest batch, the hyper-parameters baked into the launches); a call
+ * with another set, or one behind a call that made the plan move one of its lazily grown buffers (more particles than
+ * any call before it), captures again. */
+int pyz_sgld_run_info(const pyz_mlp *mlp, int32_t *h_captures);
+
 /* Non-finite sentinel (the reference prints the loss every step, Optimizer.py:123, so a diverged chain is
  * seen at once; here losses stay on the device): every kernel that finalises a step's loss counts NaN / Inf
  * results.  Synchronises `stream`, returns PYZ_E_NAN if any step since the last call was non-finite (the
