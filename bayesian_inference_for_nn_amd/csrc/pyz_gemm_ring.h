@@ -154,8 +154,11 @@ __global__ void __launch_bounds__(64 * NW) k_dense_fwd_ring(DenseArgs g) {
   const float *wl = g.theta + (long long)p * g.theta_pstride + g.w_off;
   const int mis = (int)((reinterpret_cast<uintptr_t>(wl) & 15u) >> 2);      // floats between the aligned base and W[0][0]
   const float *wl_al = wl - mis;
-  // bytes from the aligned base to the end of the (P, D) parameter matrix: loads past it return zero
-  const long long b_bytes = ((long long)(P - p) * g.theta_pstride - g.w_off + mis) * 4;
+  // bytes from the aligned base to &W[K][0], the end of this layer's W: the range check is per dword, loads past it return
+  // zero.  The rows k >= K of the last slab (K % KS != 0) are therefore zeros, not the bias row, the following layers and
+  // the NEXT PARTICLE's first weights: those met the zeros staged for A, and 0 x Inf = NaN carried one diverged particle
+  // into its neighbour.  (Every column < N of row K - 1 is inside: ((K - 1) N + col + mis) < K N + mis.)
+  const long long b_bytes = ((long long)K * N + mis) * 4;
   const __amdgpu_buffer_rsrc_t rB =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(wl_al), 0, (int)(b_bytes < 0x7fffffffLL ? b_bytes : 0x7fffffffLL), 0x00020000);
   constexpr unsigned OOB = 0x80000000u;                   // stays out of range under the per-slab advance (D * 4 < 2^31)
@@ -413,16 +416,17 @@ static inline int pyz_fwd_ring_variant(const DenseArgs &g, int grid_batch, int P
   return 0;
 }
 
-template <int NL, int NCT, int SUB, int NW>
-static inline void pyz_launch_fwd_ring_as(const DenseArgs &g, int grid_batch, int P, hipStream_t st) {
-  DenseArgs a = g;
-  a.n_part = P;
-  a.grid_rows = grid_batch;
-  a.n_cgrp = g.N > 200 ? (g.N + 199) / 200 : 1;
-  a.cgrp_w = g.N > 200 ? 200 : g.N;
-  const long long wgs = (long long)((grid_batch + 31) / 32) * P * a.n_cgrp;
-  PYZ_LAUNCH((k_dense_fwd_ring<NL, NCT, SUB, NW>), dim3((unsigned)((wgs + 7) / 8 * 8)), dim3(64 * NW), 0, st, a);
-}
+// (a macro: the launch probe records the kernel expression as written, so the instantiation is spelled out at the launch)
+#define PYZ_LAUNCH_FWD_RING_AS(SUB, NW)                                                                                      \
+  do {                                                                                                                       \
+    DenseArgs a = g;                                                                                                         \
+    a.n_part = P;                                                                                                            \
+    a.grid_rows = grid_batch;                                                                                                \
+    a.n_cgrp = g.N > 200 ? (g.N + 199) / 200 : 1;                                                                            \
+    a.cgrp_w = g.N > 200 ? 200 : g.N;                                                                                        \
+    const long long wgs_ = (long long)((grid_batch + 31) / 32) * P * a.n_cgrp;                                               \
+    PYZ_LAUNCH((k_dense_fwd_ring<204, 13, SUB, NW>), dim3((unsigned)((wgs_ + 7) / 8 * 8)), dim3(64 * NW), 0, st, a);         \
+  } while (0)
 
 // the split-reduction form for a single chain's hidden layer of <= 200 units (C2: 1024 x 784 -> 200 is 32 row blocks; cut
 // into k_split ranges of slabs it is 256 workgroups): caller checked the shape (pyz_fwd_ring_ksplit_ok) and set part_out
@@ -451,10 +455,10 @@ static inline bool pyz_launch_fwd_ring(const DenseArgs &g, int grid_batch, int P
       static const int sub_env = pyz_env_int("PYZ_FWD_RING_SUB", 0), nw = pyz_env_int("PYZ_FWD_RING_WAVES", 8);
       const long long wgs = (long long)((grid_batch + 31) / 32) * P * (g.N > 200 ? (g.N + 199) / 200 : 1);
       const int sub = sub_env ? sub_env : (4 * wgs <= 5 * (long long)pyz_cu_count() ? 2 : 1);
-      if (nw == 4 && sub == 2) pyz_launch_fwd_ring_as<204, 13, 2, 4>(g, grid_batch, P, st);
-      else if (nw == 4) pyz_launch_fwd_ring_as<204, 13, 1, 4>(g, grid_batch, P, st);
-      else if (sub == 2) pyz_launch_fwd_ring_as<204, 13, 2, 8>(g, grid_batch, P, st);
-      else pyz_launch_fwd_ring_as<204, 13, 1, 8>(g, grid_batch, P, st);
+      if (nw == 4 && sub == 2) PYZ_LAUNCH_FWD_RING_AS(2, 4);
+      else if (nw == 4) PYZ_LAUNCH_FWD_RING_AS(1, 4);
+      else if (sub == 2) PYZ_LAUNCH_FWD_RING_AS(2, 8);
+      else PYZ_LAUNCH_FWD_RING_AS(1, 8);
       return true;
     }
     default: return false;
