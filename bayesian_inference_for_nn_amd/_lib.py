@@ -62,6 +62,13 @@ SIGNATURES = {
     "pyz_sgd_run": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _i64, _p, C.c_int, _p]),
     "pyz_swag_run": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int,
                                _i64, _i64, _p, C.c_int, _p]),
+    "pyz_sgd_members_step": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_int, _f, _i64, C.c_int, _p, _p]),
+    "pyz_sgd_members_run": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _i64,
+                                      _i64, _p, C.c_int, _p]),
+    "pyz_swag_members_step": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int, _f, _i64, C.c_int, C.c_int,
+                                        _p, _p]),
+    "pyz_swag_members_run": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.POINTER(_i32),
+                                       C.POINTER(_f), C.c_int, _i64, _i64, _p, C.c_int, _p]),
     "pyz_last_run_info": (C.c_int, [_p, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "pyz_sgld_run_info": (C.c_int, [_p, C.POINTER(_i32)]),
     "pyz_check_finite": (C.c_int, [_p, _p]),

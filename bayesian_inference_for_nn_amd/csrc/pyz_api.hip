@@ -23,6 +23,7 @@
 #include "pyz_rng.h"
 #include "pyz_sgld_chains.h"
 #include "pyz_sgld_lanes.h"
+#include "pyz_members.h"
 
 namespace {
 
@@ -1584,9 +1585,11 @@ int pyz_sgld_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, co
 // and k_sgld_update_chains behind it.  SGLD lanes (pyz_sgld_lanes.h) are the same step with a learning rate per lane and
 // the seed seed + c * seed_stride: k_sgld_update_lanes stands where k_sgld_update_chains stands, nothing else differs.
 // `lanes`: the P rows are lanes -- their host rates h_lr and seed_stride are checked as well, and at most PYZ_MAX_LANES go.
+// `row`: what the P rows are called in the messages when they are neither ("member": pyz_members.h).
 static int sgld_rows_check(const pyz_mlp *m, bool lanes, const void *theta, const void *mean, const void *sq, int P,
-                           const void *x, const void *y, const void *h_lr, const void *losses, int64_t n, int seed_stride) {
-  const char *row = lanes ? "lane" : "chain";
+                           const void *x, const void *y, const void *h_lr, const void *losses, int64_t n, int seed_stride,
+                           const char *row = nullptr) {
+  if (!row) row = lanes ? "lane" : "chain";
   if (P < 1) return pyz_fail(PYZ_E_INVALID, "n_%ss %d: at least one %s", row, P, row);
   if (n < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
   if (lanes && seed_stride != 0 && seed_stride != 1)
@@ -1606,12 +1609,21 @@ static dim3 sgld_rows_grid(long long groups, int P) {
   return dim3((unsigned)std::min<long long>(cdiv(groups, 256), per_row), (unsigned)P);
 }
 
+// The third update kind of the rows step: SGD / SWAG members (pyz_members.h, k_members_update) instead of SGLD chains or lanes.
+struct MembersUpdate {
+  bool swag;          // SWAG rows (else SGD rows: sq and dev unused)
+  float *dev;         // (P, k, D)
+  int k;
+  int freq;           // a run: hit steps and deviation columns follow from the count on the device
+  int hit, col;       // an eager step: the caller's flag and column
+};
+
 // lane_lr: the P host rates of this step's lanes (k_sgld_update_lanes, seed + c * seed_stride), or nullptr for chains
-// (k_sgld_update_chains: ctl->lr, seed + c)
+// (k_sgld_update_chains: ctl->lr, seed + c); members: the rows are ensemble members (k_members_update: ctl->lr, no noise)
 static void launch_sgld_rows_step(pyz_mlp *m, float *theta, float *mean, float *sq, int P, const float *x, const void *y,
                                   const int32_t *row_idx, int grid_batch, int slot, bool chained, long long row_stride,
                                   uint64_t seed, const float *lane_lr, int seed_stride, const float *unit_noise, float *loss,
-                                  hipStream_t st) {
+                                  hipStream_t st, const MembersUpdate *members = nullptr) {
   const StepCtl *ctl = m->ctl + slot;
   WgradArgs u{};
   u.mode = PYZ_UPD_NONE;
@@ -1621,6 +1633,32 @@ static void launch_sgld_rows_step(pyz_mlp *m, float *theta, float *mean, float *
   if (fused) u.ploss = m->scal;      // per-particle losses in the weight-gradient launch (every particle's spare workgroup)
   launch_loss_backward(m, theta, m->D, P, x, y, row_idx, grid_batch, ctl, true, u, st);
   if (!fused) PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, ctl, m->scal, m->nonfinite);
+  if (members) {
+    MembersArgs g{};
+    g.theta = theta;
+    g.mean = mean;
+    g.sq_mean = members->swag ? sq : nullptr;
+    g.dev = members->swag ? members->dev : nullptr;
+    g.grad = m->grad;
+    g.D = m->D;
+    g.grad_pstride = m->D;
+    g.groups = (m->D + 3) / 4;
+    g.ctl = ctl;
+    g.next = chained ? m->ctl + (slot ^ 1) : nullptr;
+    g.tab_bs = m->tab_bs;
+    g.tab_lr = m->tab_lr;
+    g.row_stride = row_stride;
+    g.ploss = m->scal;
+    g.loss = loss;
+    g.loss_indexed = chained ? 1 : 0;
+    g.swag = members->swag ? 1 : 0;
+    g.k = members->k;
+    g.freq = members->freq;
+    g.hit = members->hit;
+    g.col = members->col;
+    PYZ_LAUNCH(k_members_update, sgld_rows_grid(g.groups, P), dim3(256), 0, st, g);
+    return;
+  }
   SgldChainsArgs a{};
   a.theta = theta;
   a.mean = mean;
@@ -1655,14 +1693,15 @@ static void launch_sgld_rows_step(pyz_mlp *m, float *theta, float *mean, float *
 // rate is lane 0's, the update reads the launch's own).
 static int sgld_rows_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, int P, const float *d_x,
                           const void *d_y, const int32_t *d_row_idx, int batch, float lr, const float *lane_lr, int64_t n,
-                          uint64_t seed, int seed_stride, const float *d_unit_noise, float *d_loss, void *stream) {
+                          uint64_t seed, int seed_stride, const float *d_unit_noise, float *d_loss, void *stream,
+                          const MembersUpdate *members = nullptr) {
   int rc;
   if ((rc = check_call(m, P, batch))) return rc;
   if ((rc = need_grad(m, P))) return rc;
   hipStream_t st = as_stream(stream);
   set_ctl_lazy(m, batch, lr, n);   // the first kernel of the pass carries the step scalars
   launch_sgld_rows_step(m, d_theta, d_mean, d_sq_mean, P, d_x, d_y, d_row_idx, batch, 0, false, 0, seed, lane_lr, seed_stride,
-                        d_unit_noise, d_loss, st);
+                        d_unit_noise, d_loss, st, members);
   PYZ_LAUNCH_CHECK();
   return PYZ_OK;
 }
@@ -1693,8 +1732,9 @@ int pyz_sgld_lanes_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_m
 static int sgld_rows_run(pyz_mlp *m, bool lanes, float *d_theta, float *d_mean, float *d_sq_mean, int P, const float *d_x,
                          const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
                          int n_steps, int64_t n0, int64_t slot0, uint64_t seed, int seed_stride, float *d_losses,
-                         void *stream) {
-  int rc = sgld_rows_check(m, lanes, d_theta, d_mean, d_sq_mean, P, d_x, d_y, h_lr, d_losses, n0, seed_stride);
+                         void *stream, const MembersUpdate *members = nullptr) {
+  int rc = sgld_rows_check(m, lanes, d_theta, d_mean, d_sq_mean, P, d_x, d_y, h_lr, d_losses, n0, seed_stride,
+                           members ? "member" : nullptr);
   if (rc) return rc;
   if (!d_row_idx || !h_batch_sizes || !h_lr) return pyz_fail(PYZ_E_INVALID, "null pointer");
   if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
@@ -1709,7 +1749,7 @@ static int sgld_rows_run(pyz_mlp *m, bool lanes, float *d_theta, float *d_mean, 
   m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
   for (int s = 0; s < n_steps; ++s) {
     launch_sgld_rows_step(m, d_theta, d_mean, d_sq_mean, P, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true, row_stride,
-                          seed, lanes ? h_lr + (size_t)s * P : nullptr, seed_stride, nullptr, d_losses, st);
+                          seed, lanes ? h_lr + (size_t)s * P : nullptr, seed_stride, nullptr, d_losses, st, members);
     ++m->run_eager_steps;
   }
   PYZ_LAUNCH_CHECK();
@@ -1731,6 +1771,72 @@ int pyz_sgld_lanes_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_me
                        void *stream) {
   return sgld_rows_run(m, true, d_theta, d_mean, d_sq_mean, n_lanes, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, n0,
                        slot0, seed, seed_stride, d_losses, stream);
+}
+
+// ---- SGD / SWAG members (pyz_members.h): P ensemble members per launch.  The rows step of the SGLD chains above with
+// k_members_update behind the gradient pass; checks, grid rule and run loop are the ones chains use, so a run equals the
+// step calls bit for bit on ragged batches, and use_graph is accepted and reported eager, as there.
+static int members_check(const MembersUpdate &u, int frequency, bool run) {
+  if (run && frequency < 1) return pyz_fail(PYZ_E_INVALID, "frequency %d: at least 1", frequency);
+  if (u.swag && u.k < 1) return pyz_fail(PYZ_E_INVALID, "k %d: at least one deviation column", u.k);
+  if (u.swag && !u.dev) return pyz_fail(PYZ_E_INVALID, "null deviation pointer");
+  if (u.swag && !run && u.col >= u.k) return pyz_fail(PYZ_E_INVALID, "deviation column %d outside the %d of a member", u.col, u.k);
+  return PYZ_OK;
+}
+
+// SGD.py:42-84 for n_members models at once: theta <- theta - lr grad per member; with update_mean (the caller's
+// n % frequency == 0) the member's row of d_mean receives the new weights (SGD.py:78-84).
+int pyz_sgd_members_step(pyz_mlp *m, float *d_theta, float *d_mean, int n_members, const float *d_x, const void *d_y,
+                         const int32_t *d_row_idx, int batch, float lr, int64_t n, int update_mean, float *d_loss,
+                         void *stream) {
+  const MembersUpdate u{false, nullptr, 0, 0, update_mean ? 1 : 0, -1};
+  const int rc = sgld_rows_check(m, false, d_theta, d_mean, d_mean, n_members, d_x, d_y, nullptr, d_loss, n, 0, "member");
+  return rc ? rc : sgld_rows_step(m, d_theta, d_mean, nullptr, n_members, d_x, d_y, d_row_idx, batch, lr, nullptr, n, 0, 0,
+                                  nullptr, d_loss, stream, &u);
+}
+
+// The SGD train loop (SGD.py:42-84 inside Optimizer.py:121-134) of n_members models as one device-resident run: the hit
+// steps follow from the count n0 + s on the device, so the run is not cut where the "mean" is taken.
+int pyz_sgd_members_run(pyz_mlp *m, float *d_theta, float *d_mean, int n_members, int frequency, const float *d_x,
+                        const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
+                        int n_steps, int64_t n0, int64_t slot0, float *d_losses, int use_graph, void *stream) {
+  (void)use_graph;
+  const MembersUpdate u{false, nullptr, 0, frequency, 0, -1};
+  const int rc = members_check(u, frequency, true);
+  return rc ? rc : sgld_rows_run(m, false, d_theta, d_mean, d_mean, n_members, d_x, d_y, d_row_idx, h_batch_sizes, h_lr,
+                                 n_steps, n0, slot0, 0, 0, d_losses, stream, &u);
+}
+
+// SWAG.py:61-92 for n_members models at once: pyz_swag_step's update per member; with update_moments the member's moments
+// move and theta - mean goes to column dev_col of the member's (k, D) block of d_dev (dev_col < 0: to no column, as
+// pyz_swag_step's d_dev_row = NULL).
+int pyz_swag_members_step(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, float *d_dev, int k, int n_members,
+                          const float *d_x, const void *d_y, const int32_t *d_row_idx, int batch, float lr, int64_t n,
+                          int update_moments, int dev_col, float *d_loss, void *stream) {
+  const MembersUpdate u{true, d_dev, k, 0, update_moments ? 1 : 0, dev_col};
+  int rc = members_check(u, 1, false);
+  if (rc) return rc;
+  rc = sgld_rows_check(m, false, d_theta, d_mean, d_sq_mean, n_members, d_x, d_y, nullptr, d_loss, n, 0, "member");
+  return rc ? rc : sgld_rows_step(m, d_theta, d_mean, d_sq_mean, n_members, d_x, d_y, d_row_idx, batch, lr, nullptr, n, 0, 0,
+                                  nullptr, d_loss, stream, &u);
+}
+
+// The SWAG train loop (SWAG.py:43-94 inside Optimizer.py:121-134) of n_members models as one device-resident run.  As in
+// pyz_swag_run the bookkeeping follows from the step count on the device: the members must have started at count 0 with
+// every step run, so the first step of a call cannot have a count below its slot.
+int pyz_swag_members_run(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, float *d_dev, int k, int frequency,
+                         int n_members, const float *d_x, const void *d_y, const int32_t *d_row_idx,
+                         const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0, int64_t slot0,
+                         float *d_losses, int use_graph, void *stream) {
+  (void)use_graph;
+  const MembersUpdate u{true, d_dev, k, frequency, 0, -1};
+  const int rc = members_check(u, frequency, true);
+  if (rc) return rc;
+  if (n0 >= 0 && slot0 >= 0 && n0 < slot0)
+    return pyz_fail(PYZ_E_INVALID, "count %lld below slot %lld: the members did not start at count 0", (long long)n0,
+                    (long long)slot0);
+  return sgld_rows_run(m, false, d_theta, d_mean, d_sq_mean, n_members, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, n0,
+                       slot0, 0, 0, d_losses, stream, &u);
 }
 
 // ---- the scores of SGLD lanes (pyz_sgld_lanes.h)

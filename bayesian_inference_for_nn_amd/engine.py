@@ -289,6 +289,73 @@ class MLPPlan:
                                            lr, n_steps, int(n0), int(slot0), int(seed), ptr(losses_out),
                                            1 if use_graph else 0, _stream()))
 
+    def _check_members(self, theta, mean, sq_mean=None, dev=None):
+        """The (n_members, D) state of SGD / SWAG members (dev: (n_members, k, D)); returns (n_members, k)."""
+        P = int(theta.shape[0]) if theta.dim() == 2 else 0
+        if not 1 <= P <= self.max_particles:
+            raise ValueError(f"theta must be (n_members, {self.D}) with 1 <= n_members <= {self.max_particles}")
+        for t, nm in ((theta, "theta"), (mean, "mean")) + (((sq_mean, "sq_mean"),) if dev is not None else ()):
+            _f32(t, (P, self.D), nm)
+        k = 0
+        if dev is not None:
+            _f32(dev, name="dev")
+            if dev.dim() != 3 or dev.shape[0] != P or dev.shape[1] < 1 or dev.shape[2] != self.D:
+                raise ValueError(f"dev must be ({P}, k, {self.D}) with k >= 1")
+            k = int(dev.shape[1])
+        return P, k
+
+    def sgd_members_step(self, theta, mean, x, y, lr, n, update_mean, loss_out, batch=None, row_idx=None):
+        """One SGD step of the n_members rows of theta (n_members, D) on ONE shared batch; with update_mean the rows of
+        mean receive the new weights (SGD.py:78-84); loss_out: (n_members,) float32."""
+        P, _ = self._check_members(theta, mean)
+        batch = self._check_rows_step(P, x, y, loss_out, batch, row_idx, None)
+        check(self.lib.pyz_sgd_members_step(self.h, ptr(theta), ptr(mean), P, ptr(x), ptr(y), ptr(row_idx), batch, float(lr),
+                                            int(n), 1 if update_mean else 0, ptr(loss_out), _stream()))
+
+    def sgd_members_run(self, theta, mean, frequency, x, y, row_idx, batch_sizes: Sequence[int], lrs: Sequence[float], n0,
+                        losses_out, use_graph=True, slot0=0):
+        """n = len(batch_sizes) steps of sgd_members_step without host work in between (see sgld_run for the tables): step
+        s has count n0 + s and copies the weights to mean when frequency divides it; losses_out: float32
+        (slots, n_members), step s writes row slot0 + s."""
+        P, _ = self._check_members(theta, mean)
+        n_steps = len(batch_sizes)
+        if len(lrs) != n_steps or n_steps < 1:
+            raise ValueError("one learning rate per step, at least one step")
+        bs = self._check_rows_run(P, "n_members", x, y, row_idx, batch_sizes, losses_out, slot0)
+        lr = (C.c_float * n_steps)(*[float(v) for v in lrs])
+        check(self.lib.pyz_sgd_members_run(self.h, ptr(theta), ptr(mean), P, int(frequency), ptr(x), ptr(y), ptr(row_idx), bs,
+                                           lr, n_steps, int(n0), int(slot0), ptr(losses_out), 1 if use_graph else 0,
+                                           _stream()))
+
+    def swag_members_step(self, theta, mean, sq_mean, dev, x, y, lr, n, update_moments, dev_col, loss_out, batch=None,
+                          row_idx=None):
+        """One SWAG step of the n_members rows of theta / mean / sq_mean (n_members, D) on ONE shared batch; dev is
+        (n_members, k, D).  With update_moments the moments move and theta - mean goes to row dev_col of every member's
+        block (dev_col None: to no row); loss_out: (n_members,) float32."""
+        P, k = self._check_members(theta, mean, sq_mean, dev)
+        col = -1 if dev_col is None else int(dev_col)
+        if col >= k:
+            raise ValueError(f"dev_col {col} outside the {k} rows of a member")
+        batch = self._check_rows_step(P, x, y, loss_out, batch, row_idx, None)
+        check(self.lib.pyz_swag_members_step(self.h, ptr(theta), ptr(mean), ptr(sq_mean), ptr(dev), k, P, ptr(x), ptr(y),
+                                             ptr(row_idx), batch, float(lr), int(n), 1 if update_moments else 0, col,
+                                             ptr(loss_out), _stream()))
+
+    def swag_members_run(self, theta, mean, sq_mean, dev, frequency, x, y, row_idx, batch_sizes: Sequence[int],
+                         lrs: Sequence[float], n0, losses_out, use_graph=True, slot0=0):
+        """n = len(batch_sizes) steps of swag_members_step without host work in between: the hit steps and the deviation
+        row follow from the count n0 + s on the device (the members started at count 0); losses_out: float32
+        (slots, n_members), step s writes row slot0 + s."""
+        P, k = self._check_members(theta, mean, sq_mean, dev)
+        n_steps = len(batch_sizes)
+        if len(lrs) != n_steps or n_steps < 1:
+            raise ValueError("one learning rate per step, at least one step")
+        bs = self._check_rows_run(P, "n_members", x, y, row_idx, batch_sizes, losses_out, slot0)
+        lr = (C.c_float * n_steps)(*[float(v) for v in lrs])
+        check(self.lib.pyz_swag_members_run(self.h, ptr(theta), ptr(mean), ptr(sq_mean), ptr(dev), k, int(frequency), P,
+                                            ptr(x), ptr(y), ptr(row_idx), bs, lr, n_steps, int(n0), int(slot0),
+                                            ptr(losses_out), 1 if use_graph else 0, _stream()))
+
     def _lane_rates(self, lrs, shape):
         """Host float32 rates of the lanes, C-contiguous, of the given shape ((P,) for a step, (n_steps, P) for a run)."""
         lr = np.ascontiguousarray(np.asarray(lrs, dtype=np.float32))

@@ -238,6 +238,49 @@ int pyz_swag_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, 
                  const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0,
                  int64_t slot0, float *d_losses, int use_graph, void *stream);
 
+/* ---- SGD / SWAG members: n_members models trained in one particle-batched step (an extension: the reference trains
+ * one; P of them are a deep ensemble, or the components of a MultiSWAG mixture).  The state is float32 (n_members, D)
+ * row-major; all members take their gradients on the SAME batch (one particle-batched pass, as pyz_sgld_chains_step),
+ * then member c's row takes the single-model update.  d_loss[c] / d_losses[(slot0 + s) * n_members + c] = member c's
+ * batch loss.  PYZ_E_INVALID, with no device touched: a null plan, a null pointer among the required ones,
+ * n_members < 1, k < 1, frequency < 1, a negative count.  PYZ_E_SHAPE: n_members above the plan's max_particles, a
+ * batch outside the plan.  The runs enqueue every step for its own batch size (no hipGraph, whatever use_graph says:
+ * pyz_last_run_info reports eager steps), nothing synchronises inside the call, and the results equal n_steps calls of
+ * the step bit for bit, on ragged batches and across epoch changes.
+ *
+ * pyz_sgd_members_step (SGD.py:42-84): theta <- theta - lr grad per member; with update_mean != 0 (the caller's
+ * n % frequency == 0) row c of d_mean receives member c's new weights, else d_mean is neither read nor written. */
+int pyz_sgd_members_step(pyz_mlp *mlp, float *d_theta, float *d_mean, int n_members, const float *d_x,
+                         const void *d_y, const int32_t *d_row_idx, int batch, float lr, int64_t n, int update_mean,
+                         float *d_loss /* [n_members] */, void *stream);
+
+/* The train loop over pyz_sgd_members_step (SGD.py:42-84 inside Optimizer.py:121-134): step s has count n0 + s and
+ * copies the weights to d_mean when that count is a multiple of `frequency` -- decided on the device, so the run is
+ * not cut there as the single-model caller of pyz_sgd_run cuts it. */
+int pyz_sgd_members_run(pyz_mlp *mlp, float *d_theta, float *d_mean, int n_members, int frequency, const float *d_x,
+                        const void *d_y, const int32_t *d_row_idx, const int32_t *h_batch_sizes, const float *h_lr,
+                        int n_steps, int64_t n0, int64_t slot0, float *d_losses /* (slots, n_members) */,
+                        int use_graph, void *stream);
+
+/* pyz_swag_members_step (SWAG.py:61-92): pyz_swag_step's update per member, in its float32 expressions.  d_dev is
+ * float32 (n_members, k, D): member c's k deviation rows, each one column of the reference's deviation matrix.  With
+ * update_moments != 0 the moments move and theta - mean goes to row dev_col of every member's block; dev_col < 0
+ * writes no row (pyz_swag_step's d_dev_row = NULL), dev_col >= k is PYZ_E_INVALID.  Without update_moments the
+ * moments and deviations are neither read nor written. */
+int pyz_swag_members_step(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, float *d_dev, int k,
+                          int n_members, const float *d_x, const void *d_y, const int32_t *d_row_idx, int batch,
+                          float lr, int64_t n, int update_moments, int dev_col, float *d_loss /* [n_members] */,
+                          void *stream);
+
+/* The train loop over pyz_swag_members_step (SWAG.py:43-94 inside Optimizer.py:121-134): the bookkeeping of
+ * pyz_swag_run per member -- moments on the counts that are multiples of `frequency`, the deviation into row
+ * min(ceil(count / frequency), k - 1) -- which assumes the members started at count 0 with every step run: n0 < slot0
+ * is PYZ_E_INVALID. */
+int pyz_swag_members_run(pyz_mlp *mlp, float *d_theta, float *d_mean, float *d_sq_mean, float *d_dev, int k,
+                         int frequency, int n_members, const float *d_x, const void *d_y, const int32_t *d_row_idx,
+                         const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0, int64_t slot0,
+                         float *d_losses /* (slots, n_members) */, int use_graph, void *stream);
+
 /* What the last pyz_sgld_run / pyz_sgd_run / pyz_swag_run call on this plan did: steps that ran inside replayed
  * hipGraphs, steps launched eagerly, and the number of graph launches.  With use_graph != 0 on a non-NULL
  * stream a run of any length is replayed from graphs: chunks of 32 steps (PYZ_GRAPH_STEPS) and one graph for
