@@ -45,31 +45,19 @@ class BSAM(_AdamFamily):
 
     def step(self, save_document_path=None):
         idx, b, new_epoch = self._next_batch()
-        self._seen_batches += 1                                # BSAM.py:49-50
+        self._count_batch(new_epoch)                           # BSAM.py:49-57: before this step's update
         self._total_batches += 1
-        if new_epoch:                                          # BSAM.py:52-57: before this step's update
-            self._seen_batches = 1
-            self._running_dev.zero_()
-            self._epoch_num += 1
         self._plan.bsam_step(self._theta, self._m_dev, self._v_dev, self._x_dev, self._y_dev, self._lr, self._beta_1,
                              self._beta_2, self._lam, self._rho, self._gam, self._num_data, self._n, self._seed,
                              self._loss_dev, batch=b, row_idx=idx)
         self._running_dev += self._loss_dev.sum()              # BSAM.py:73,97
         if save_document_path != None:
             l1, l2 = self._loss_dev.tolist()
-            with open(save_document_path, "a") as losses_file:
-                losses_file.write(str(l1))
-                losses_file.write(str(l2))
+            self._append_loss(save_document_path, str(l1) + str(l2))
         self._n += 1
         return DeviceScalar(self._running_dev.clone(), 0, 1.0 / self._seen_batches)
 
-    _losses_per_step = 2                                       # l1, l2
-
-    def _run_losses(self, n_steps):
-        import torch
-        if getattr(self, "_res_losses2", None) is None or self._res_losses2.numel() < 2 * self._res_cap:
-            self._res_losses2 = torch.zeros(2 * self._res_cap, device="cuda")
-        return self._res_losses2
+    _loss_cols = 2                                             # l1, l2
 
     def _launch_run(self, row_idx, losses, sizes, lrs, epochs, s0):
         self._plan.bsam_run(self._theta, self._m_dev, self._v_dev, self._x_dev, self._y_dev, row_idx, sizes, lrs,

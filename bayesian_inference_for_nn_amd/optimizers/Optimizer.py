@@ -16,6 +16,33 @@ from ..losses import loss_kind
 from ..nn.model import Array
 
 
+def run_epochs(epoch_num: int, epoch_starts, n_steps: int):
+    """The epoch count each of n_steps consecutive steps uses for its bias correction, as the step loop counts it
+    (ADAM.py:49-55: a step that opens a new epoch increments the count BEFORE its update).  epoch_num: the count before
+    the first of them; epoch_starts: the steps (0-based) among them that open a new epoch."""
+    starts = sorted(int(s) for s in epoch_starts)
+    epochs, k = [], 0
+    for s in range(int(n_steps)):
+        while k < len(starts) and starts[k] <= s:
+            k += 1
+        epochs.append(int(epoch_num) + k)
+    return epochs
+
+
+def fold_running(running, step_losses, last_epoch_start=None):
+    """The epoch's running loss after a run, as the step loop's float32 `running += loss` leaves it (ADAM.py:49-56): summed
+    one step after the other, onto the old value -- or from zero at the last step that opened an epoch.  step_losses: (n,)
+    the loss of each step, or (n, 2) BSAM's l1, l2, which the step adds as fl(l1 + l2)."""
+    a = np.asarray(step_losses, dtype=np.float32)
+    if a.ndim == 2:
+        a = (a[:, 0] + a[:, 1]).astype(np.float32)
+    start = np.float32(running)
+    if last_epoch_start is not None:
+        start, a = np.float32(0.0), a[int(last_epoch_start):]
+    # cumsum is sequential by construction (a pairwise sum would round differently)
+    return np.cumsum(np.concatenate([np.asarray([start], dtype=np.float32), a]), dtype=np.float32)[-1]
+
+
 class DeviceScalar:
     """A loss that stays on the device until somebody looks at it (``Optimizer.train`` prints the
     loss every step when verbose: Optimizer.py:123 -- formatting is what triggers the sync)."""
@@ -117,9 +144,76 @@ class Optimizer(ABC):
         if self._verbose:
             print()
 
+    # ------------------------------------------------------------------ quiet train(): device-resident runs
     def _train_resident(self, nb_iterations: int) -> bool:
-        """Hook: run all iterations without per-step host work (returns False if unsupported)."""
+        """verbose=False, no loss file, no model saving: all steps in device-resident runs (hipGraph replay, no per-step
+        host work), planned and launched chunk by chunk.  False sends train() to the step loop: for a model the class's run
+        does not take -- decided before anything is planned or enqueued -- or if the library refuses the first chunk, whose
+        batches are then given back to the iterator.  A refusal after a chunk went out is raised: those steps have run.
+        A class provides _resident_supported, _resident_launch and _after_resident."""
+        from .._lib import PyzError
+        if not self._resident_supported():
+            return False
+        if nb_iterations <= 0:
+            return True
+        saved = (self._perm_host, self._perm_dev, self._pos, self._epoch, self._rng.bit_generator.state)
+        try:
+            losses = self._run_resident_chunks(nb_iterations, self._resident_launch(nb_iterations))
+        except PyzError:
+            if self._run_chunks > 0:
+                raise
+            self._perm_host, self._perm_dev, self._pos, self._epoch = saved[:4]
+            self._rng.bit_generator.state = saved[4]
+            return False
+        self._after_resident(nb_iterations, losses)
+        return True
+
+    def _resident_supported(self) -> bool:
+        """Hook: whether this optimizer's device-resident run takes the compiled model."""
         return False
+
+    def _fused_head(self) -> bool:
+        """The chained SGD / SWAG / BBB / ADAM runs need the fused step: a last layer of at most 32 units."""
+        return self._spec.dims[-1] <= 32
+
+    def _resident_launch(self, nb_iterations: int):
+        """Hook: launch(row_idx, losses, batch_sizes, s0) of _run_resident_chunks for a run of nb_iterations steps."""
+        raise NotImplementedError
+
+    def _after_resident(self, nb_iterations: int, losses):
+        """Hook: step()'s bookkeeping for the nb_iterations steps a run just took; losses: their rows of the loss buffer.
+        The steps that opened an epoch are in _run_epoch_starts."""
+        raise NotImplementedError
+
+    # ------------------------------------------------------------------ what step() keeps, and its replay after a run
+    def _count_batch(self, new_epoch: bool):
+        """The epoch prelude of step() (SGD.py:45-54, ADAM.py:46-55): a step that opens an epoch restarts the epoch's
+        batch count and running loss BEFORE its update."""
+        self._seen_batches += 1
+        if new_epoch:
+            self._seen_batches = 1
+            self._running_dev.zero_()
+            self._epoch_num += 1
+
+    def _count_run(self, n_steps: int, step_losses):
+        """_count_batch and `running += loss` for the n_steps a run just took (step_losses: see _fold_run)."""
+        starts = self._run_epoch_starts
+        self._seen_batches = self._seen_batches + n_steps if not starts else n_steps - starts[-1]
+        self._epoch_num += len(starts)
+        self._fold_run(step_losses, starts[-1] if starts else None)
+
+    def _fold_run(self, step_losses, last_epoch_start=None):
+        """_running_dev after a run, bit for bit what the step loop's float32 `running += loss` leaves (fold_running).
+        step_losses: device (n,) the scalar each step adds, or (n, 2) BSAM's l1, l2.  (The host has joined the run.)"""
+        start = 0.0 if last_epoch_start is not None else self._running_dev.item()      # read only where it counts
+        self._running_dev.fill_(float(fold_running(start, step_losses.cpu().numpy(), last_epoch_start)))
+
+    @staticmethod
+    def _append_loss(path, text: str):
+        """The loss file of train(loss_save_document_path=...): a step's `text` appended, worded by its class (reading
+        the loss synchronises, so step() calls this only where a path was given)."""
+        with open(path, "a") as losses_file:
+            losses_file.write(text)
 
     def _print_progress(self, progress: float, bar_length=10, suffix="Training", **kwargs):
         """One carriage-returned status line: "<suffix> <pct> % [====>     ] key: value ..." (the text the
@@ -228,6 +322,10 @@ class Optimizer(ABC):
             s += nb
         return torch.as_tensor(table), sizes
 
+    # floats a step of the resident run writes to the loss buffer: None, one loss, a (cap,) buffer; k, a (cap, k) buffer --
+    # a loss per chain, lane or member (set at compile), BSAM's l1, l2, BBB's four costs
+    _loss_cols = None
+
     def _reserve_resident(self, n_steps: int):
         """Persistent device buffers for the device-resident runs: the row-index table and the per-step losses.
         Their addresses are baked into the library's captured hipGraph, so they are kept (and only grown)
@@ -236,20 +334,15 @@ class Optimizer(ABC):
         if n_steps > getattr(self, "_res_cap", 0):
             cap = max(256, 1 << (n_steps - 1).bit_length())
             self._res_idx = torch.zeros((cap, self._plan.max_batch), dtype=torch.int32, device="cuda")
-            self._res_losses = torch.zeros(cap, device="cuda")
+            self._res_losses = torch.zeros(cap if self._loss_cols is None else (cap, self._loss_cols), device="cuda")
             self._res_cap = cap
-
-    def _resident_buffers(self, table, n_steps: int):
-        """(row-index table, loss buffer) on the device with `table` in the first n_steps slots."""
-        self._reserve_resident(n_steps)
-        self._res_idx[:n_steps].copy_(table)
-        return self._res_idx, self._res_losses
 
     # steps in the first chunk of a resident run, growth from chunk to chunk, largest chunk: laying out a step's batch
     # costs the host about 15 us (one permutation per epoch), the device takes 24 us for it at C2 -- a chunk may be at most
     # 1.6 times the one the device is working through, or the device waits for its plan; the first chunk is small because
     # the device idles while it is planned
     _resident_chunks = (32, 1.5, 512)
+    _ONE_CHUNK = (1 << 62, 1.0, 1 << 62)             # the policy of a run that is planned and launched in one piece
 
     def _run_stream(self):
         """The stream of this optimizer's device-resident runs (graph replay needs a stream of its own)."""
@@ -285,20 +378,24 @@ class Optimizer(ABC):
         """A device-resident run, planned and launched in chunks: the host lays out the batches of the next chunk
         (one permutation per epoch) while the device works through the current one.
         launch(row_idx, losses, batch_sizes, s0) enqueues steps [s0, s0 + len(batch_sizes)) on the current stream;
-        returns the losses of the run (a view of the persistent buffer)."""
+        returns the losses of the run (a view of the persistent buffer).  Records the steps of the run that opened an
+        epoch (_run_epoch_starts, known to the launch of their chunk) and the chunks that went out (_run_chunks)."""
         import torch
         first, growth, largest = self._resident_chunks
         self._reserve_resident(nb_iterations)
         main, stream = torch.cuda.current_stream(), self._run_stream()
+        self._run_epoch_starts, self._run_chunks = [], 0
         s0, size = 0, float(first)
         while s0 < nb_iterations:
             n = min(max(1, int(size)), nb_iterations - s0)
             size = min(size * growth, float(largest))
             table, sizes = self._batch_plan(n)
+            self._run_epoch_starts += [s0 + e for e in self._plan_epoch_starts]
             self._res_idx[s0:s0 + n].copy_(table)
             stream.wait_stream(main)
             with torch.cuda.stream(stream):
                 launch(self._res_idx, self._res_losses, sizes, s0)
+            self._run_chunks += 1
             s0 += n
         self._join_run(stream)
         self._warn_if_diverged(stream)

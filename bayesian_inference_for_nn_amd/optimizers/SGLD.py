@@ -173,6 +173,7 @@ class SGLD(Optimizer):
         self._mean_dev = torch.zeros((P, self._D), device="cuda")
         self._sq_mean_dev = torch.zeros((P, self._D), device="cuda")
         self._loss_dev = torch.zeros(P, device="cuda")
+        self._loss_cols = P                                    # a loss per chain (lane) and step
         self._running_dev = torch.zeros(1, device="cuda")
         self._weight_layers_indices = self._layer_indices()
         self._n = 0
@@ -190,8 +191,7 @@ class SGLD(Optimizer):
                                         self._seed, self._loss_dev, batch=b, row_idx=idx)
         self._running_dev += self._loss_dev.mean()             # the mean over chains of the batch loss
         if save_document_path != None:
-            with open(save_document_path, "a") as losses_file:
-                losses_file.write(str(float(self._loss_dev.mean().item())))
+            self._append_loss(save_document_path, str(float(self._loss_dev.mean().item())))
         self._n += 1
         return DeviceScalar(self._running_dev.clone(), 0, 1.0 / self._n)
 
@@ -206,8 +206,7 @@ class SGLD(Optimizer):
                              self._seed, self._loss_dev, batch=b, row_idx=idx)
         self._running_dev += self._loss_dev                        # SGLD.py:58
         if save_document_path != None:
-            with open(save_document_path, "a") as losses_file:
-                losses_file.write(str(float(self._loss_dev.item())))
+            self._append_loss(save_document_path, str(float(self._loss_dev.item())))
         self._n += 1
         return DeviceScalar(self._running_dev.clone(), 0, 1.0 / self._n)
 
@@ -218,40 +217,32 @@ class SGLD(Optimizer):
         super().train(nb_iterations, loss_save_document_path, model_save_frequency, model_save_path,
                       weights_and_biases_log)
 
-    def _train_resident(self, nb_iterations: int) -> bool:
-        """verbose=False: all steps in one device-resident run (hipGraph replay, no host sync)."""
-        import torch
-        rows = self._lanes is not None or self._n_chains > 1       # a (P, D) state: the loss buffer holds a row per step
+    # ------------------------------------------------------------------ quiet train(): device-resident runs
+    def _resident_supported(self):
+        return True                                                # pyz_sgld_run and the rows runs take unfused models
+
+    def _resident_launch(self, nb_iterations):
         if self._lanes is not None:
             rates = self._lane_rates(self._n, nb_iterations)
 
-            def launch(idx, loss_buf, sizes, s0):
+            def launch(idx, losses, sizes, s0):
                 self._plan.sgld_lanes_run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
-                                          rates[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf,
+                                          rates[s0:s0 + len(sizes)], self._n + s0, self._seed, losses,
                                           seed_stride=self._lane_stride, slot0=s0)
-        else:
-            lrs = np.asarray(self._lr(self._n + np.arange(nb_iterations, dtype=np.float64))).astype(np.float32).tolist()
-            run = self._plan.sgld_chains_run if rows else self._plan.sgld_run
+            return launch
+        lrs = np.asarray(self._lr(self._n + np.arange(nb_iterations, dtype=np.float64))).astype(np.float32).tolist()
+        run = self._plan.sgld_chains_run if self._n_chains > 1 else self._plan.sgld_run
 
-            def launch(idx, loss_buf, sizes, s0):
-                run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
-                    lrs[s0:s0 + len(sizes)], self._n + s0, self._seed, loss_buf, use_graph=True, slot0=s0)
-        losses = self._run_resident_chunks(nb_iterations, launch)
-        self._running_dev += losses.mean(dim=1).sum() if rows else losses.sum()   # rows: the mean over chains of a step
+        def launch(idx, losses, sizes, s0):
+            run(self._theta, self._mean_dev, self._sq_mean_dev, self._x_dev, self._y_dev, idx, sizes,
+                lrs[s0:s0 + len(sizes)], self._n + s0, self._seed, losses, use_graph=True, slot0=s0)
+        return launch
+
+    def _after_resident(self, nb_iterations, losses):
+        # a (P, D) state has a loss per chain and step: a step adds their mean; the sum runs over epochs (SGLD.py:58)
+        self._fold_run(losses if self._loss_cols is None else losses.mean(dim=1))
         self._n += nb_iterations
         self.last_losses = losses.clone()          # the buffer itself is reused by the next run
-        return True
-
-    def _reserve_resident(self, n_steps: int):
-        """With n_chains = P > 1 the loss buffer of the resident runs is (cap, P): a row per step."""
-        import torch
-        if self._n_chains == 1 and self._lanes is None:
-            return super()._reserve_resident(n_steps)
-        if n_steps > getattr(self, "_res_cap", 0):
-            cap = max(256, 1 << (n_steps - 1).bit_length())
-            self._res_idx = torch.zeros((cap, self._plan.max_batch), dtype=torch.int32, device="cuda")
-            self._res_losses = torch.zeros((cap, self._n_chains), device="cuda")
-            self._res_cap = cap
 
     def update_parameters_step(self):
         return super().update_parameters_step()

@@ -35,32 +35,10 @@ class SWAG(Optimizer):
         self._n_members = 1
 
     def compile_extra_components(self, **kwargs):
+        """A plan for P = n_members particles; the state is (D,) with (k, D) deviation rows for one member, the
+        reference's path, and (P, D) with (P, k, D) rows for several (see the module docstring for the starts)."""
         import torch
-        self._n_members = _members.n_members_of(kwargs)
-        if self._n_members > 1:
-            return self._compile_members(**kwargs)
-        self._k = int(self._hyperparameters.k)
-        self._frequency = int(self._hyperparameters.frequency)
-        self._lr = self._hyperparameters.lr
-        self._scale = self._hyperparameters.scale
-        self._batch_size = int(self._hyperparameters.batch_size)
-        self._setup_backend(seed=kwargs.get("seed"))
-        self._net.set_weights(kwargs["starting_model"].get_weights())     # SWAG.py:107-108
-        self._base_model = self._net
-        self._dataset_setup()
-        self._theta = torch.as_tensor(self._net.weights_flat.copy()).cuda()
-        self._mean_dev = torch.zeros(self._D, device="cuda")               # SWAG.py:113-127
-        self._sq_mean_dev = torch.zeros(self._D, device="cuda")
-        self._dev_rows = torch.zeros((self._k, self._D), device="cuda")    # row c = column c of the reference's matrix
-        self._n_cols = 0
-        self._loss_dev = torch.zeros(1, device="cuda")
-        self._weight_layers_indices = self._layer_indices()
-        self._n = 0
-
-    def _compile_members(self, **kwargs):
-        """n_members = P > 1: a plan for P particles, a (P, D) state and (P, k, D) deviation rows."""
-        import torch
-        P = self._n_members
+        P = self._n_members = _members.n_members_of(kwargs)
         self._k = int(self._hyperparameters.k)
         self._frequency = int(self._hyperparameters.frequency)
         self._lr = self._hyperparameters.lr
@@ -69,91 +47,61 @@ class SWAG(Optimizer):
         start = kwargs["starting_model"]
         _members.check_starts(start, P)
         self._setup_backend(seed=kwargs.get("seed"), max_particles=P, chains_per_rank=P)
-        self._theta = torch.as_tensor(_members.member_starts(self, start, P)).cuda()
+        rows = _members.member_starts(self, start, P)          # SWAG.py:107-108: the starting model's weights are copied
+        self._theta = torch.as_tensor(rows if P > 1 else rows[0]).cuda()
         self._base_model = self._net
         self._dataset_setup()
-        self._mean_dev = torch.zeros((P, self._D), device="cuda")
-        self._sq_mean_dev = torch.zeros((P, self._D), device="cuda")
-        self._dev_rows = torch.zeros((P, self._k, self._D), device="cuda")   # [c, r] = column r of member c's matrix
+        lead = (P,) if P > 1 else ()
+        self._mean_dev = torch.zeros(lead + (self._D,), device="cuda")     # SWAG.py:113-127
+        self._sq_mean_dev = torch.zeros(lead + (self._D,), device="cuda")
+        # row r (of member c) = column r of the reference's (member c's) matrix
+        self._dev_rows = torch.zeros(lead + (self._k, self._D), device="cuda")
         self._n_cols = 0
         self._loss_dev = torch.zeros(P, device="cuda")
+        self._loss_cols = P if P > 1 else None                 # a loss per member and step
         self._weight_layers_indices = self._layer_indices()
         self._n = 0
 
-    def _reserve_resident(self, n_steps: int):
-        if self._n_members == 1:
-            return super()._reserve_resident(n_steps)
-        _members.reserve_resident(self, n_steps, self._n_members)
-
-    def _step_members(self, save_document_path=None):
-        idx, b, _ = self._next_batch()
-        update = self._n % self._frequency == 0
-        col = min(self._n_cols, self._k - 1)                   # append until k, then replace the last (SWAG.py:85-89)
-        self._plan.swag_members_step(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows, self._x_dev,
-                                     self._y_dev, self._lr, self._n, update, col if update else None, self._loss_dev,
-                                     batch=b, row_idx=idx)
-        if update and self._n_cols < self._k:
-            self._n_cols += 1
-        if save_document_path != None:
-            with open(save_document_path, "a") as losses_file:
-                losses_file.write(str(float(self._loss_dev.mean().item())))
-        self._n += 1
-        return DeviceScalar(self._loss_dev.mean().reshape(1), 0)   # the mean over members of the batch loss
-
-    def _train_resident_members(self, nb_iterations: int) -> bool:
-        if nb_iterations <= 0:
-            return True
-
-        def launch(idx, loss_buf, sizes, s0):
-            self._plan.swag_members_run(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows, self._frequency,
-                                        self._x_dev, self._y_dev, idx, sizes, [float(self._lr)] * len(sizes),
-                                        self._n + s0, loss_buf, slot0=s0)
-        losses = self._run_resident_chunks(nb_iterations, launch)
-        self._n += nb_iterations
-        self._n_cols = min(self._k, -(-self._n // self._frequency))      # hits among counts 0 .. n - 1
-        self._loss_dev.copy_(losses[-1])
-        self.last_losses = losses.clone()          # (n, P); the buffer itself is reused by the next run
-        return True
-
     def step(self, save_document_path=None):
-        if self._n_members > 1:
-            return self._step_members(save_document_path)
         idx, b, _ = self._next_batch()
         update = self._n % self._frequency == 0                             # SWAG.py:72
         # columns are appended until there are k; afterwards the LAST one is replaced (SWAG.py:85-89, as written)
         col = min(self._n_cols, self._k - 1)
-        self._plan.swag_step(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows[col] if update else None,
-                             self._x_dev, self._y_dev, self._lr, self._n, update, self._loss_dev, batch=b, row_idx=idx)
+        if self._n_members > 1:
+            self._plan.swag_members_step(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows, self._x_dev,
+                                         self._y_dev, self._lr, self._n, update, col if update else None, self._loss_dev,
+                                         batch=b, row_idx=idx)
+            loss = self._loss_dev.mean().reshape(1)            # the mean over members of the batch loss
+        else:
+            self._plan.swag_step(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows[col] if update else None,
+                                 self._x_dev, self._y_dev, self._lr, self._n, update, self._loss_dev, batch=b, row_idx=idx)
+            loss = self._loss_dev.clone()
         if update and self._n_cols < self._k:
             self._n_cols += 1
         if save_document_path != None:
-            with open(save_document_path, "a") as losses_file:
-                losses_file.write(str(float(self._loss_dev.item())))
+            self._append_loss(save_document_path, str(float(loss.item())))
         self._n += 1
-        return DeviceScalar(self._loss_dev.clone(), 0)
+        return DeviceScalar(loss, 0)
 
-    def _train_resident(self, nb_iterations: int) -> bool:
-        """verbose=False: all steps in one device-resident run; the moment / deviation-column bookkeeping is a
-        function of the step count and runs on the device (the chain starts at count 0: compile sets it)."""
-        import torch
-        from .._lib import PyzError
-        if self._n_members > 1:
-            return self._train_resident_members(nb_iterations)
-        if nb_iterations <= 0:
-            return True
-        def launch(idx, loss_buf, sizes, s0):
-            self._plan.swag_run(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows, self._frequency,
-                                self._x_dev, self._y_dev, idx, sizes, [float(self._lr)] * len(sizes), self._n + s0,
-                                loss_buf, slot0=s0)
-        try:
-            losses = self._run_resident_chunks(nb_iterations, launch)
-        except PyzError:                              # shapes the fused step does not take: per-step loop
-            return False
+    # ------------------------------------------------------------------ quiet train(): device-resident runs
+    def _resident_supported(self):
+        return self._n_members > 1 or self._fused_head()
+
+    def _resident_launch(self, nb_iterations):
+        """The moment / deviation-column bookkeeping is a function of the step count and runs on the device (the chain
+        starts at count 0: compile sets it)."""
+        run = self._plan.swag_members_run if self._n_members > 1 else self._plan.swag_run
+
+        def launch(idx, losses, sizes, s0):
+            run(self._theta, self._mean_dev, self._sq_mean_dev, self._dev_rows, self._frequency, self._x_dev, self._y_dev,
+                idx, sizes, [float(self._lr)] * len(sizes), self._n + s0, losses, slot0=s0)
+        return launch
+
+    def _after_resident(self, nb_iterations, losses):
         self._n += nb_iterations
         self._n_cols = min(self._k, -(-self._n // self._frequency))      # hits among counts 0 .. n - 1
-        self._loss_dev.copy_(losses[-1:])
-        self.last_losses = losses.clone()          # the buffer itself is reused by the next run
-        return True
+        self._loss_dev.copy_(losses[-1].reshape(self._loss_dev.shape))
+        self.last_losses = losses.clone()          # (n,) or (n, P); the buffer itself is reused by the next run
 
     def update_parameters_step(self):
         pass

@@ -1,5 +1,5 @@
 """What SGD and SWAG share for n_members = P > 1 (an extension: the reference trains one model per optimizer): the
-members' starting points and the (cap, P) loss buffer of their device-resident runs."""
+members' starting points (with P = 1: the one model's, as the reference copies it)."""
 
 import numpy as np
 
@@ -36,12 +36,3 @@ def member_starts(opt, start, P: int) -> np.ndarray:
     opt._net.set_flat(rows[0])
     return np.stack(rows).astype(np.float32)
 
-
-def reserve_resident(opt, n_steps: int, P: int):
-    """Optimizer._reserve_resident with a (cap, P) loss buffer: a row per step, as SGLD's chains have."""
-    import torch
-    if n_steps > getattr(opt, "_res_cap", 0):
-        cap = max(256, 1 << (n_steps - 1).bit_length())
-        opt._res_idx = torch.zeros((cap, opt._plan.max_batch), dtype=torch.int32, device="cuda")
-        opt._res_losses = torch.zeros((cap, P), device="cuda")
-        opt._res_cap = cap

@@ -27,7 +27,8 @@ s = io.StringIO(); pstats.Stats(pr, stream=s).sort_stats("cumulative").print_sta
 # the same 2000 steps through the plan directly, on the optimizer's own buffers: one call, then the optimizer's chunks
 import numpy as np
 table, sizes = opt._batch_plan(2000)
-idx, losses = opt._resident_buffers(table, 2000)
+idx, losses = opt._res_idx, opt._res_losses                  # (train(2000) above left them large enough)
+idx[:2000].copy_(table)
 lrs = np.asarray(opt._lr(opt._n + np.arange(2000, dtype=np.float64))).astype(np.float32).tolist()
 st = torch.cuda.Stream()
 def direct(chunks):
