@@ -128,6 +128,18 @@ SIGNATURES = {
     "pyz_download": (C.c_int, [_p, _p, C.c_size_t, _p]),
     "pyz_sync": (C.c_int, [_p]),
     "pyz_wait_flags": (C.c_int, [_p, C.c_int, C.c_uint64, C.c_int, _p, _p]),
+    "pyz_stem_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i32), C.c_int, C.c_int, C.POINTER(_p)]),
+    "pyz_stem_destroy": (C.c_int, [_p]),
+    "pyz_stem_param_count": (_i64, [_p]),
+    "pyz_stem_feature_count": (_i64, [_p]),
+    "pyz_stem_workspace_bytes": (_i64, [_p]),
+    "pyz_stem_forward": (C.c_int, [_p, _p, _i64, C.c_int, _p, _p, C.c_int, _p, _p]),
+    "pyz_stem_backward": (C.c_int, [_p, _p, _i64, C.c_int, _p, _p, C.c_int, _p, _p, _i64, _p]),
+    "pyz_convnet_forward": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, C.c_int, _p, _p]),
+    "pyz_convnet_loss_grad": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_int, _p, _p, _p]),
+    "pyz_convnet_sgd_step": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, _f, _p, _p]),
+    "pyz_convnet_swag_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int, _f, _i64, C.c_int, _p, _p]),
+    "pyz_convnet_predict": (C.c_int, [_p, _p, _p, C.c_int, _p, C.c_int, _p, _p, _p, _p]),
 }
 
 E_NAN = -6

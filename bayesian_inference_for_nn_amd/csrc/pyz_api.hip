@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pyz_common.h"
+#include "pyz_conv.h"
 #include "pyz_corrupt.h"
 #include "pyz_fsvi.h"
 #include "pyz_fused.h"
@@ -211,10 +212,12 @@ DenseArgs forward_args(pyz_mlp *m, int l, const float *theta, long long theta_ps
 // forward over layers [0, l_end); activations land in m->act[l]
 void launch_forward(pyz_mlp *m, const float *theta, long long theta_ps, int P, const float *x,
                     const int32_t *row_idx, int grid_batch, const StepCtl *ctl, hipStream_t st,
-                    float *gather_out = nullptr, int l_end = -1, const StepCtl *gate = nullptr, int gate_mod = 0) {
+                    float *gather_out = nullptr, int l_end = -1, const StepCtl *gate = nullptr, int gate_mod = 0,
+                    long long x_pstride = 0) {
   if (l_end < 0) l_end = m->L;
   for (int l = 0; l < l_end; ++l) {
     DenseArgs g = forward_args(m, l, theta, theta_ps, x, row_idx, ctl, gather_out);
+    if (l == 0) g.in_pstride = x_pstride;   // (a conv net's Dense tail: one set of rows, the stem's features, per particle)
     g.wt = pyz_wt_for(P);
     g.gate = gate;
     g.gate_mod = gate_mod;
@@ -249,13 +252,22 @@ void launch_loss(pyz_mlp *m, int P, const void *y, const int32_t *row_idx, int g
 
 inline int loss_nblk(const pyz_mlp *m, int grid_batch) { return std::min(cdiv(m->max_batch, 256), cdiv(grid_batch, 256)); }
 
+// The Dense tail of a conv net (pyz_convnet_*): its rows x are the stem's features, one set per particle; its gradient block
+// sits inside the (P, D_total) gradient of the whole vector; and layer 0 has a data gradient too, towards the features.
+struct TailOf {
+  long long x_pstride;      // particle stride of x (and of dfeat)
+  long long grad_pstride;   // row stride of grad
+  float *dfeat;             // (P, max_batch, dims[0]): d loss / d features, times act_feat' of the features
+  int act_feat;
+};
+
 // grad_sq (one chain only): the weight-gradient kernels also write the batch mean of the squared per-example gradients there
 void launch_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, const float *x,
                      const int32_t *row_idx, int grid_batch, const StepCtl *ctl, float *grad, hipStream_t st,
-                     float *grad_sq = nullptr) {
+                     float *grad_sq = nullptr, const TailOf *tail = nullptr) {
   for (int l = m->L - 1; l >= 0; --l) {
     const int K = m->dims[l], N = m->dims[l + 1];
-    if (l > 0) {  // delta[l-1] = (delta[l] W_l^T) * act'(h_{l-1})
+    if (l > 0 || tail) {  // delta[l-1] = (delta[l] W_l^T) * act'(h_{l-1}); layer 0 of a tail: the same towards the features
       DenseArgs g{};
       g.K = K;
       g.N = N;
@@ -265,11 +277,11 @@ void launch_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, 
       g.theta = theta;
       g.theta_pstride = theta_ps;
       g.w_off = m->w_off[l];
-      g.out = m->delta[l - 1];
-      g.out_pstride = (long long)m->max_batch * K;
-      g.aux = m->act[l - 1];
-      g.aux_pstride = (long long)m->max_batch * K;
-      g.act = m->acts[l - 1];
+      g.out = l > 0 ? m->delta[l - 1] : tail->dfeat;
+      g.out_pstride = l > 0 ? (long long)m->max_batch * K : tail->x_pstride;
+      g.aux = l > 0 ? m->act[l - 1] : x;
+      g.aux_pstride = g.out_pstride;
+      g.act = l > 0 ? m->acts[l - 1] : tail->act_feat;
       g.vec = (N % 8 == 0) && (m->w_off[l] % 4 == 0) && (P == 1 || theta_ps % 4 == 0) && aligned16(theta) ? 1 : 0;
       g.ctl = ctl;
       pyz_launch_bwd_data(g, grid_batch, P, st);
@@ -279,7 +291,7 @@ void launch_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, 
     g.N = N;
     if (l == 0) {
       g.in = x;
-      g.in_pstride = 0;
+      g.in_pstride = tail ? tail->x_pstride : 0;
       g.row_idx = row_idx;
     } else {
       g.in = m->act[l - 1];
@@ -289,7 +301,7 @@ void launch_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, 
     g.aux = m->delta[l];
     g.aux_pstride = (long long)m->max_batch * N;
     g.out = grad;
-    g.out_pstride = m->D;
+    g.out_pstride = tail ? tail->grad_pstride : m->D;
     g.w_off = m->w_off[l];
     g.ctl = ctl;
     if (grad_sq) pyz_launch_bwd_weight_sq(g, grad_sq, grid_batch, st);
@@ -3758,6 +3770,460 @@ int pyz_debug_stamps(uint64_t *h_out, int64_t n_words) {
   (void)n_words;
   return pyz_fail(PYZ_E_INVALID, "not a PYZ_STAMPS build");
 #endif
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- conv nets: a stem (pyz_conv.h) in front of a Dense tail
+struct StemOp {
+  int kind = 0;
+  int H = 0, W = 0, C = 0;         // input map
+  int OH = 0, OW = 0, N = 0;       // output map (a pool keeps C)
+  int kh = 0, kw = 0, pt = 0, pl = 0, act = 0;   // conv: kernel, top / left padding, activation; pool: kh x kw windows
+  int K = 0, KT = 0;               // conv: taps, and table entries (taps + bias, padded to even)
+  long long w_off = 0;
+  int2 *ktab = nullptr;
+  float *out = nullptr, *delta = nullptr;   // (max_p, max_batch, OH * OW * N) each
+  int32_t *win = nullptr;          // pool: the winners
+  long long size() const { return (long long)OH * OW * N; }
+};
+
+struct pyz_stem {
+  int n_ops = 0;
+  StemOp op[PYZ_STEM_MAX_OPS];
+  int in_h = 0, in_w = 0, in_c = 0, max_batch = 0, max_p = 0;
+  long long D = 0, F = 0;
+  size_t ws_bytes = 0;
+  float *part = nullptr;           // partial tiles of the weight gradients (stem_part_bytes)
+  bool forwarded = false;          // a forward has left every op's output in the workspace
+};
+
+namespace {
+
+// rows of one range of the weight-gradient reduction: a function of the plan alone, so the split (and with it the order
+// of the sums) does not depend on the batch of the call
+inline int stem_rows_per_range(const pyz_stem *s, const StemOp &o) {
+  const long long m_max = (long long)s->max_batch * o.OH * o.OW;
+  return (int)std::max<long long>(256, ((m_max + 255) / 256 + 1) / 2 * 2);
+}
+
+int stem_check(const pyz_stem *s, int P, int batch) {
+  if (!s) return pyz_fail(PYZ_E_INVALID, "null stem");
+  if (batch <= 0 || batch > s->max_batch) return pyz_fail(PYZ_E_SHAPE, "batch %d outside [1, %d] of the plan", batch, s->max_batch);
+  if (P <= 0 || P > s->max_p) return pyz_fail(PYZ_E_SHAPE, "particle count %d outside [1, %d] of the plan", P, s->max_p);
+  return PYZ_OK;
+}
+
+ConvArgs conv_args(const pyz_stem *s, int o, const float *theta, long long theta_ps, const float *x, const int32_t *row_idx, int batch) {
+  const StemOp &c = s->op[o];
+  ConvArgs g{};
+  if (o == 0) {
+    g.in = x;
+    g.in_pstride = 0;
+    g.row_idx = row_idx;
+  } else {
+    g.in = s->op[o - 1].out;
+    g.in_pstride = (long long)s->max_batch * s->op[o - 1].size();
+  }
+  g.theta = theta;
+  g.theta_pstride = theta_ps;
+  g.w_off = c.w_off;
+  g.out = c.out;
+  g.out_pstride = (long long)s->max_batch * c.size();
+  g.delta = c.delta;
+  g.delta_pstride = g.out_pstride;
+  g.ktab = c.ktab;
+  g.batch = batch;
+  g.M = batch * c.OH * c.OW;
+  g.H = c.H; g.W = c.W; g.C = c.C; g.OH = c.OH; g.OW = c.OW; g.N = c.N; g.K = c.K; g.KT = c.KT;
+  g.kh = c.kh; g.kw = c.kw; g.pt = c.pt; g.pl = c.pl; g.act = c.act;
+  g.inv_ohw = 1.0f / (float)(c.OH * c.OW);
+  g.inv_ow = 1.0f / (float)c.OW;
+  return g;
+}
+
+PoolArgs pool_args(const pyz_stem *s, int o, int batch) {
+  const StemOp &q = s->op[o], &c = s->op[o - 1];
+  PoolArgs g{};
+  g.in = c.out;
+  g.in_pstride = (long long)s->max_batch * c.size();
+  g.out = q.out;
+  g.out_pstride = (long long)s->max_batch * q.size();
+  g.win = q.win;
+  g.dout = q.delta;
+  g.din = c.delta;
+  g.batch = batch;
+  g.H = q.H; g.W = q.W; g.C = q.C; g.OH = q.OH; g.OW = q.OW; g.ph = q.kh; g.pw = q.kw;
+  g.act_below = c.act;
+  return g;
+}
+
+inline int conv_waves(long long tiles, int steps) {
+  int S = 1;
+  while (S < PYZ_CONV_WAVES && tiles * S < 1024 && steps >= 16 * S) S *= 2;
+  return S;
+}
+
+// every op's output into the workspace; the last one's is the features (P, max_batch, F)
+void stem_forward(pyz_stem *s, const float *theta, long long theta_ps, int P, const float *x, const int32_t *row_idx, int batch,
+                  hipStream_t st) {
+  for (int o = 0; o < s->n_ops; ++o) {
+    const StemOp &c = s->op[o];
+    if (c.kind == PYZ_STEM_CONV) {
+      ConvArgs g = conv_args(s, o, theta, theta_ps, x, row_idx, batch);
+      const long long tiles = (long long)((g.M + 31) / 32) * ((g.N + 31) / 32);
+      const int S = conv_waves(tiles * P, g.KT / 2);
+      PYZ_LAUNCH(k_conv_fwd, dim3((unsigned)tiles, P), dim3(64 * S), (size_t)g.KT * 8 + (S > 1 ? S * 4096 : 0), st, g);
+    } else {
+      PoolArgs g = pool_args(s, o, batch);
+      PYZ_LAUNCH(k_pool_fwd, dim3((unsigned)cdiv((long long)batch * c.size(), 256), P), dim3(256), 0, st, g);
+    }
+  }
+  s->forwarded = true;
+}
+
+// bytes of the partial-tile slab of the weight-gradient reductions: the largest conv's (P, G, tiles, 32 x 32)
+size_t stem_part_bytes(const pyz_stem *s) {
+  size_t need = 0;
+  for (int o = 0; o < s->n_ops; ++o) {
+    const StemOp &c = s->op[o];
+    if (c.kind != PYZ_STEM_CONV) continue;
+    const long long tiles = (long long)((c.K + 1 + 31) / 32) * ((c.N + 31) / 32);
+    const long long G = cdiv((long long)s->max_batch * c.OH * c.OW, stem_rows_per_range(s, c));
+    need = std::max(need, sizeof(float) * (size_t)(s->max_p * G * tiles * 1024));
+  }
+  return need;
+}
+
+// the stem's block of the gradient from the last op's delta (a conv's: d loss / d pre-activation; a pool's: d loss / d out)
+void stem_backward(pyz_stem *s, const float *theta, long long theta_ps, int P, const float *x, const int32_t *row_idx, int batch,
+                   float *grad, long long grad_ps, hipStream_t st) {
+  for (int o = s->n_ops - 1; o >= 0; --o) {
+    const StemOp &c = s->op[o];
+    if (c.kind == PYZ_STEM_POOL) {
+      PoolArgs g = pool_args(s, o, batch);
+      PYZ_LAUNCH(k_pool_bwd, dim3((unsigned)cdiv((long long)batch * c.H * c.W * c.C, 256), P), dim3(256), 0, st, g);
+      continue;
+    }
+    ConvArgs g = conv_args(s, o, theta, theta_ps, x, row_idx, batch);
+    g.rows_per_g = stem_rows_per_range(s, c);
+    g.G = cdiv(g.M, g.rows_per_g);
+    g.part = s->part;
+    g.grad = grad;
+    g.grad_pstride = grad_ps;
+    const long long tiles = (long long)((g.K + 1 + 31) / 32) * ((g.N + 31) / 32);
+    const int S = conv_waves(tiles * g.G * P, std::min(g.M, g.rows_per_g) / 2);
+    PYZ_LAUNCH(k_conv_wgrad, dim3((unsigned)(tiles * g.G), P), dim3(64 * S), (S > 1 ? S * 4096 : 0) + PYZ_WGRAD_CHUNK * 16, st, g);
+    PYZ_LAUNCH(k_conv_wgrad_reduce, dim3((unsigned)cdiv((long long)(g.K + 1) * g.N, 16), P), dim3(256), 0, st, g);
+    if (o > 0) {   // (not launched for the first conv: nothing is below it)
+      const StemOp &b = s->op[o - 1];
+      g.out = b.delta;
+      g.out_pstride = (long long)s->max_batch * b.size();
+      g.below = b.kind == PYZ_STEM_CONV ? b.out : nullptr;
+      g.below_pstride = g.out_pstride;
+      g.act_below = b.act;
+      PYZ_LAUNCH(k_conv_dgrad, dim3((unsigned)cdiv((long long)batch * c.H * c.W * c.C, 256), P), dim3(256), 0, st, g);
+    }
+  }
+}
+
+int convnet_check(const pyz_stem *s, const pyz_mlp *m, int P, int batch) {
+  int rc = stem_check(s, P, batch);
+  if (rc) return rc;
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  // the conv net's loss goes through launch_loss (k_loss_scce / k_loss_mse), which has no BinaryCrossentropy arm: on a Dense
+  // net that loss always takes the fused head (one output unit)
+  if (m->loss == PYZ_LOSS_BCE) return pyz_fail(PYZ_E_INVALID, "BinaryCrossentropy is not built for a conv net: use a softmax head with SparseCategoricalCrossentropy, or MeanSquaredError");
+  if (m->dims[0] != s->F || m->max_batch != s->max_batch || m->max_p != s->max_p)
+    return pyz_fail(PYZ_E_INVALID, "the Dense plan (input %d, max_batch %d, max_particles %d) does not continue the stem (%lld features, %d, %d)",
+                    m->dims[0], m->max_batch, m->max_p, s->F, s->max_batch, s->max_p);
+  return PYZ_OK;
+}
+
+inline const float *stem_features(const pyz_stem *s) { return s->op[s->n_ops - 1].out; }
+
+// stem + Dense forward; the Dense outputs land in m->act
+void convnet_forward(pyz_stem *s, pyz_mlp *m, const float *theta, int P, const float *x, const int32_t *row_idx, int batch,
+                     hipStream_t st) {
+  const long long Dt = s->D + m->D;
+  stem_forward(s, theta, Dt, P, x, row_idx, batch, st);
+  launch_forward(m, theta + s->D, Dt, P, stem_features(s), nullptr, batch, m->ctl, st, nullptr, -1, nullptr, 0,
+                 (long long)s->max_batch * s->F);
+}
+
+// forward, loss and (grad != null) the gradient of the whole vector into grad (P, D_total).  The callers have set the plan's
+// ctl with set_ctl(..., row_off = 0, ...), and that zero matters: the stem's kernels read row_idx[b] as it stands, k_loss_*
+// read row_idx[ctl->row_off + m] -- the images and the labels are the same rows only while row_off is 0 (a chained run,
+// which moves row_off, would have to hand the stem row_idx + row_off)
+int convnet_loss_backward(pyz_stem *s, pyz_mlp *m, const float *theta, int P, const float *x, const void *y,
+                          const int32_t *row_idx, int batch, float *grad, hipStream_t st) {
+  const long long Dt = s->D + m->D;
+  convnet_forward(s, m, theta, P, x, row_idx, batch, st);
+  launch_loss(m, P, y, row_idx, batch, m->ctl, grad != nullptr, st);   // the labels go through row_idx; the features are in batch order
+  m->cur_nblk = loss_nblk(m, batch);
+  if (!grad) return PYZ_OK;
+  const StemOp &last = s->op[s->n_ops - 1];
+  // (nothing has updated a weight by the time the feature gradient reads layer 0's: the updates are the callers' last launch)
+  const TailOf tail{(long long)s->max_batch * s->F, Dt, last.delta, last.kind == PYZ_STEM_CONV ? last.act : PYZ_ACT_LINEAR};
+  launch_backward(m, theta + s->D, Dt, P, stem_features(s), nullptr, batch, m->ctl, grad + s->D, st, nullptr, &tail);
+  stem_backward(s, theta, Dt, P, x, row_idx, batch, grad, Dt, st);
+  return PYZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pyz_stem_destroy(pyz_stem *s) {
+  if (!s) return PYZ_OK;
+  for (int o = 0; o < s->n_ops; ++o) {
+    void *ptrs[] = {s->op[o].ktab, s->op[o].out, s->op[o].delta, s->op[o].win};
+    for (void *p : ptrs)
+      if (p) (void)hipFree(p);
+  }
+  if (s->part) (void)hipFree(s->part);
+  delete s;
+  return PYZ_OK;
+}
+
+int pyz_stem_create(int in_h, int in_w, int in_c, int n_ops, const int32_t *h_ops, int max_batch, int max_particles,
+                    pyz_stem **out) {
+  if (!out || !h_ops) return pyz_fail(PYZ_E_INVALID, "null argument");
+  *out = nullptr;
+  if (n_ops < 1 || n_ops > PYZ_STEM_MAX_OPS) return pyz_fail(PYZ_E_INVALID, "n_ops %d outside [1, %d]", n_ops, PYZ_STEM_MAX_OPS);
+  if (in_h < 1 || in_w < 1 || in_c < 1 || in_h > 16384 || in_w > 16384)   // (positions travel as 16-bit pairs in the tap tables)
+    return pyz_fail(PYZ_E_INVALID, "input map %d x %d x %d outside [1, 16384] x [1, 16384] x [1, ..)", in_h, in_w, in_c);
+  if (max_batch < 1 || max_particles < 1 || max_particles > 65535)
+    return pyz_fail(PYZ_E_INVALID, "max_batch must be >= 1 and max_particles in [1, 65535]");
+  pyz_stem *s = new pyz_stem();
+  s->n_ops = 0;
+  s->in_h = in_h; s->in_w = in_w; s->in_c = in_c;
+  s->max_batch = max_batch;
+  s->max_p = max_particles;
+  auto fail = [&](int rc) {
+    pyz_stem_destroy(s);
+    return rc;
+  };
+  int H = in_h, W = in_w, C = in_c;
+  long long off = 0;
+  for (int o = 0; o < n_ops; ++o) {
+    const int32_t *d = h_ops + 6 * o;
+    StemOp &c = s->op[o];
+    c.kind = d[0];
+    c.H = H; c.W = W; c.C = C;
+    if (c.kind == PYZ_STEM_CONV) {
+      c.N = d[1]; c.kh = d[2]; c.kw = d[3]; c.act = d[5];
+      if (c.N < 1 || c.kh < 1 || c.kw < 1) return fail(pyz_fail(PYZ_E_INVALID, "op %d: Conv2D filters %d, kernel %d x %d", o, c.N, c.kh, c.kw));
+      if (d[4] != 0 && d[4] != 1) return fail(pyz_fail(PYZ_E_INVALID, "op %d: padding %d is neither valid (0) nor same (1)", o, d[4]));
+      if (c.act < PYZ_ACT_LINEAR || c.act > PYZ_ACT_SIGMOID) return fail(pyz_fail(PYZ_E_INVALID, "op %d: activation %d is not supported on a Conv2D", o, c.act));
+      const int ph = d[4] ? c.kh - 1 : 0, pw = d[4] ? c.kw - 1 : 0;   // TensorFlow's SAME at stride 1: k - 1 in all,
+      c.pt = ph / 2;                                                  // the smaller half on top / left
+      c.pl = pw / 2;
+      if (c.kh > H + ph || c.kw > W + pw)
+        return fail(pyz_fail(PYZ_E_SHAPE, "op %d: a %d x %d kernel is larger than the padded %d x %d image", o, c.kh, c.kw, H + ph, W + pw));
+      c.OH = H + ph - c.kh + 1;
+      c.OW = W + pw - c.kw + 1;
+      if ((long long)c.kh * c.kw * C > PYZ_CONV_MAX_K)
+        return fail(pyz_fail(PYZ_E_SHAPE, "op %d: %lld taps per filter exceed %d", o, (long long)c.kh * c.kw * C, PYZ_CONV_MAX_K));
+      c.K = c.kh * c.kw * C;
+      c.KT = (c.K + 2) & ~1;
+      c.w_off = off;
+      off += (long long)(c.K + 1) * c.N;
+    } else if (c.kind == PYZ_STEM_POOL) {
+      if (o == 0 || s->op[o - 1].kind != PYZ_STEM_CONV) return fail(pyz_fail(PYZ_E_INVALID, "op %d: a MaxPooling2D must follow a Conv2D", o));
+      c.kh = d[1]; c.kw = d[2]; c.N = C;
+      if (c.kh < 1 || c.kw < 1) return fail(pyz_fail(PYZ_E_INVALID, "op %d: pool %d x %d", o, c.kh, c.kw));
+      if (c.kh > H || c.kw > W) return fail(pyz_fail(PYZ_E_SHAPE, "op %d: a %d x %d pool is larger than its %d x %d input", o, c.kh, c.kw, H, W));
+      c.OH = H / c.kh;
+      c.OW = W / c.kw;
+    } else {
+      return fail(pyz_fail(PYZ_E_INVALID, "op %d: unknown kind %d", o, c.kind));
+    }
+    if ((long long)max_batch * c.OH * c.OW > PYZ_CONV_MAX_ROWS || (long long)max_batch * H * W * C >= (1LL << 31) ||
+        (long long)max_batch * c.size() >= (1LL << 31))
+      return fail(pyz_fail(PYZ_E_SHAPE, "op %d: max_batch %d x the %d x %d x %d map exceeds the kernels' row or index range", o, max_batch, c.OH, c.OW, c.N));
+    H = c.OH; W = c.OW; C = c.N;
+    s->n_ops = o + 1;
+  }
+  if (s->op[0].kind != PYZ_STEM_CONV) return fail(pyz_fail(PYZ_E_INVALID, "the first op must be a Conv2D"));
+  s->D = off;
+  s->F = (long long)H * W * C;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(pyz_fail(PYZ_E_NODEV, "no HIP device visible"));
+  for (int o = 0; o < n_ops; ++o) {
+    StemOp &c = s->op[o];
+    const size_t bytes = sizeof(float) * (size_t)max_particles * max_batch * c.size() + 64;
+    if (hipMalloc((void **)&c.out, bytes) != hipSuccess || hipMalloc((void **)&c.delta, bytes) != hipSuccess)
+      return fail(pyz_fail(PYZ_E_OOM, "workspace allocation of %zu bytes failed", bytes));
+    s->ws_bytes += 2 * bytes;
+    if (c.kind == PYZ_STEM_POOL) {
+      if (hipMalloc((void **)&c.win, bytes) != hipSuccess) return fail(pyz_fail(PYZ_E_OOM, "workspace allocation of %zu bytes failed", bytes));
+      s->ws_bytes += bytes;
+      continue;
+    }
+    std::vector<int2> tab(c.KT);
+    for (int k = 0; k < c.KT; ++k) {
+      if (k < c.K) {
+        const int cc = k % c.C, j = (k / c.C) % c.kw, i = k / (c.C * c.kw);
+        tab[k] = make_int2((i << 16) | j, (i * c.W + j) * c.C + cc);
+      } else {
+        tab[k] = make_int2(k == c.K ? PYZ_TAP_BIAS : PYZ_TAP_NONE, 0);
+      }
+    }
+    if (hipMalloc((void **)&c.ktab, sizeof(int2) * c.KT) != hipSuccess) return fail(pyz_fail(PYZ_E_OOM, "tap table allocation failed"));
+    if (hipMemcpy(c.ktab, tab.data(), sizeof(int2) * c.KT, hipMemcpyHostToDevice) != hipSuccess)
+      return fail(pyz_fail(PYZ_E_HIP, "tap table upload failed"));
+    s->ws_bytes += sizeof(int2) * c.KT;
+  }
+  {
+    const size_t bytes = stem_part_bytes(s);
+    if (hipMalloc((void **)&s->part, bytes) != hipSuccess) return fail(pyz_fail(PYZ_E_OOM, "workspace allocation of %zu bytes failed", bytes));
+    s->ws_bytes += bytes;
+  }
+  *out = s;
+  return PYZ_OK;
+}
+
+int64_t pyz_stem_param_count(const pyz_stem *s) { return s ? s->D : -1; }
+int64_t pyz_stem_feature_count(const pyz_stem *s) { return s ? s->F : -1; }
+int64_t pyz_stem_workspace_bytes(const pyz_stem *s) { return s ? (int64_t)s->ws_bytes : -1; }
+
+int pyz_stem_forward(pyz_stem *s, const float *d_theta, int64_t theta_stride, int P, const float *d_x, const int32_t *d_row_idx,
+                     int batch, float *d_features, void *stream) {
+  int rc = stem_check(s, P, batch);
+  if (rc) return rc;
+  if (!d_theta || !d_x || !d_features) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (theta_stride < s->D) return pyz_fail(PYZ_E_INVALID, "theta_stride %lld is smaller than the stem's %lld parameters", (long long)theta_stride, s->D);
+  hipStream_t st = as_stream(stream);
+  stem_forward(s, d_theta, theta_stride, P, d_x, d_row_idx, batch, st);
+  const long long n = (long long)batch * s->F;
+  PYZ_LAUNCH(k_stem_rows<false>, dim3((unsigned)cdiv(n, 256), P), dim3(256), 0, st, stem_features(s), (long long)s->max_batch * s->F,
+             d_features, n, n, (const float *)nullptr, 0LL, 0);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_stem_backward(pyz_stem *s, const float *d_theta, int64_t theta_stride, int P, const float *d_x, const int32_t *d_row_idx,
+                      int batch, const float *d_feature_grad, float *d_grad, int64_t grad_stride, void *stream) {
+  int rc = stem_check(s, P, batch);
+  if (rc) return rc;
+  if (!d_theta || !d_x || !d_feature_grad || !d_grad) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (theta_stride < s->D || grad_stride < s->D) return pyz_fail(PYZ_E_INVALID, "a stride is smaller than the stem's %lld parameters", s->D);
+  if (!s->forwarded) return pyz_fail(PYZ_E_INVALID, "pyz_stem_backward needs the pyz_stem_forward of the same batch before it");
+  hipStream_t st = as_stream(stream);
+  const StemOp &last = s->op[s->n_ops - 1];
+  const long long n = (long long)batch * s->F, ps = (long long)s->max_batch * s->F;
+  PYZ_LAUNCH(k_stem_rows<true>, dim3((unsigned)cdiv(n, 256), P), dim3(256), 0, st, d_feature_grad, n, last.delta, ps, n,
+             (const float *)last.out, ps, last.kind == PYZ_STEM_CONV ? last.act : PYZ_ACT_LINEAR);
+  stem_backward(s, d_theta, theta_stride, P, d_x, d_row_idx, batch, d_grad, grad_stride, st);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_convnet_forward(pyz_stem *s, pyz_mlp *m, const float *d_theta, int P, const float *d_x, const int32_t *d_row_idx,
+                        int batch, float *d_out, void *stream) {
+  int rc = convnet_check(s, m, P, batch);
+  if (rc) return rc;
+  if (!d_theta || !d_x || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, batch, 0.0f, 0, 0, 0, st))) return rc;
+  convnet_forward(s, m, d_theta, P, d_x, d_row_idx, batch, st);
+  const int C = m->dims[m->L];
+  PYZ_LAUNCH(k_forward_finish, dim3(cdiv(batch, 256), P), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C,
+             m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0, batch, d_out);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_convnet_loss_grad(pyz_stem *s, pyz_mlp *m, const float *d_theta, int P, const float *d_x, const void *d_y,
+                          const int32_t *d_row_idx, int batch, float *d_grad, float *d_loss, void *stream) {
+  int rc = convnet_check(s, m, P, batch);
+  if (rc) return rc;
+  if ((rc = check_loss_combo(m))) return rc;
+  if (!d_theta || !d_x || !d_y || !d_loss) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, batch, 0.0f, 0, 0, 0, st))) return rc;
+  if ((rc = convnet_loss_backward(s, m, d_theta, P, d_x, d_y, d_row_idx, batch, d_grad, st))) return rc;
+  PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, m->ctl, d_loss, m->nonfinite);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_convnet_sgd_step(pyz_stem *s, pyz_mlp *m, float *d_theta, const float *d_x, const void *d_y, const int32_t *d_row_idx,
+                         int batch, float lr, float *d_loss, void *stream) {
+  int rc = convnet_check(s, m, 1, batch);
+  if (rc) return rc;
+  if ((rc = check_loss_combo(m))) return rc;
+  if (!d_theta || !d_x || !d_y || !d_loss) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  const long long Dt = s->D + m->D;
+  if ((rc = ensure_bytes((void **)&m->grad, &full(m)->x.grad_cap, sizeof(float) * (size_t)Dt + 64, m))) return rc;
+  m->grad_owner = 2;
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, batch, lr, 0, 0, 0, st))) return rc;
+  if ((rc = convnet_loss_backward(s, m, d_theta, 1, d_x, d_y, d_row_idx, batch, m->grad, st))) return rc;
+  PYZ_LAUNCH(k_sgd_update, dim3(cdiv(Dt, 256)), dim3(256), 0, st, d_theta, m->grad, Dt, m->ctl, m->part, m->cur_nblk, d_loss,
+             m->nonfinite);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_convnet_swag_step(pyz_stem *s, pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_mean, float *d_dev_row,
+                          const float *d_x, const void *d_y, const int32_t *d_row_idx, int batch, float lr, int64_t n,
+                          int update_moments, float *d_loss, void *stream) {
+  int rc = convnet_check(s, m, 1, batch);
+  if (rc) return rc;
+  if ((rc = check_loss_combo(m))) return rc;
+  if (!d_theta || !d_mean || !d_sq_mean || !d_x || !d_y || !d_loss) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  if (n < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
+  const long long Dt = s->D + m->D;
+  if ((rc = ensure_bytes((void **)&m->grad, &full(m)->x.grad_cap, sizeof(float) * (size_t)Dt + 64, m))) return rc;
+  m->grad_owner = 2;
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, batch, lr, n, 0, 0, st))) return rc;
+  if ((rc = convnet_loss_backward(s, m, d_theta, 1, d_x, d_y, d_row_idx, batch, m->grad, st))) return rc;
+  PYZ_LAUNCH(k_swag_update, dim3(cdiv(Dt, 256)), dim3(256), 0, st, d_theta, d_mean, d_sq_mean, d_dev_row, m->grad, Dt,
+             update_moments ? 1 : 0, m->ctl, m->part, m->cur_nblk, d_loss, m->nonfinite);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+int pyz_convnet_predict(pyz_stem *s, pyz_mlp *m, const float *d_weights, int n_samples, const float *d_x, int n,
+                        float *d_samples, float *d_mean, float *d_m2, void *stream) {
+  if (!s || !m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (n_samples <= 0 || n <= 0) return pyz_fail(PYZ_E_INVALID, "n_samples and n must be positive");
+  int rc = convnet_check(s, m, 1, n);
+  if (rc) return rc;
+  if (!d_weights || !d_x || !d_mean) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  if ((rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st))) return rc;
+  const long long Dt = s->D + m->D;
+  const int C = m->dims[m->L];
+  const int softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
+  PredictMomentsArgs g{};
+  g.last = m->act[m->L - 1];
+  g.C = C;
+  g.pstride = (long long)m->max_batch * C;
+  g.softmax = softmax;
+  g.n = n;
+  g.mean = d_mean;
+  g.m2 = d_m2;
+  g.inv_total = 1.0f / (float)n_samples;
+  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
+    const int S = std::min(m->max_p, n_samples - s0);
+    convnet_forward(s, m, d_weights + (long long)s0 * Dt, S, d_x, nullptr, n, st);
+    if (d_m2) {   // the moments form (pyz_predict_moments)
+      g.S = S;
+      g.accumulate = s0 > 0 ? 1 : 0;
+      if (!pyz_launch_predict_moments(g, st)) return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the moments kernel's LDS", C);
+      continue;
+    }
+    PYZ_LAUNCH(k_predict_rows, dim3(cdiv(n, 256), S), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C, softmax, n,
+               d_samples ? d_samples + (long long)s0 * n * C : nullptr);
+    PYZ_LAUNCH(k_predict_mean, dim3((unsigned)cdiv((long long)n * C, 256)), dim3(256), 0, st, m->act[m->L - 1],
+               (long long)m->max_batch * C, (long long)n * C, S, d_mean, s0 > 0 ? 1 : 0, 1.0f / (float)n_samples);
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
 }
 
 }  // extern "C"

@@ -844,6 +844,264 @@ class MLPPlan:
         return xgrad, xadv, losses
 
 
+STEM_CONV, STEM_POOL = 0, 1     # PYZ_STEM_CONV / PYZ_STEM_POOL
+CONV_MAX_K = 4094               # PYZ_CONV_MAX_K (csrc/pyz_conv.h)
+
+
+@dataclass(frozen=True)
+class ConvSpec:
+    """A convolutional front end (the stem) in front of a Dense stack.  input_shape = (H, W, C), channels last;
+    ops[k] = ("conv", filters, kh, kw, "valid" | "same", activation) or ("pool", ph, pw); tail = the Dense layers on the
+    flattened (NHWC) features.  The flat vector: per conv the kernel (kh, kw, cin, cout) then the bias, then the tail."""
+    input_shape: Tuple[int, int, int]
+    ops: Tuple[tuple, ...]
+    tail: MLPSpec
+
+    def op_shapes(self):
+        """[(in (H, W, C), out (OH, OW, N))] per op; ValueError where a kernel or a pool does not fit its input."""
+        h, w, c = (int(d) for d in self.input_shape)
+        out = []
+        for k, op in enumerate(self.ops):
+            if op[0] == "conv":
+                _, f, kh, kw, pad, _ = op
+                ph, pw = (kh - 1, kw - 1) if pad == "same" else (0, 0)
+                if kh > h + ph or kw > w + pw:
+                    raise ValueError(f"op {k}: a {kh} x {kw} kernel is larger than the padded {h + ph} x {w + pw} image")
+                o = (h + ph - kh + 1, w + pw - kw + 1, int(f))
+            else:
+                _, ph, pw = op
+                if ph > h or pw > w:
+                    raise ValueError(f"op {k}: a {ph} x {pw} pool is larger than its {h} x {w} input")
+                o = (h // ph, w // pw, c)
+            out.append(((h, w, c), o))
+            h, w, c = o
+        return out
+
+    @property
+    def features(self):
+        o = self.op_shapes()[-1][1]
+        return o[0] * o[1] * o[2]
+
+    def conv_shapes(self):
+        """[(kh, kw, cin, cout)] of the conv layers, in network order."""
+        return [(op[2], op[3], i[2], op[1]) for op, (i, _) in zip(self.ops, self.op_shapes()) if op[0] == "conv"]
+
+    @property
+    def stem_params(self):
+        return sum((kh * kw * ci + 1) * co for kh, kw, ci, co in self.conv_shapes())
+
+    @property
+    def n_params(self):
+        return self.stem_params + self.tail.n_params
+
+    # what the optimizers and BayesianModel read of an MLPSpec: the Dense stack's
+    dims = property(lambda self: self.tail.dims)
+    acts = property(lambda self: self.tail.acts)
+    loss = property(lambda self: self.tail.loss)
+
+    def layer_slices(self):
+        """The flat slice of every weight layer, conv layers first, in network order."""
+        out, off = [], 0
+        for kh, kw, ci, co in self.conv_shapes():
+            n = (kh * kw * ci + 1) * co
+            out.append(slice(off, off + n))
+            off += n
+        return out + [slice(s.start + off, s.stop + off) for s in self.tail.layer_slices()]
+
+    def variable_shapes(self):
+        return [((kh, kw, ci, co), (co,)) for kh, kw, ci, co in self.conv_shapes()] + self.tail.variable_shapes()
+
+
+class ConvPlan:
+    """Owns one `pyz_stem` handle and the MLPPlan of the Dense tail: the forward, gradient, SGD / SWAG step and read-out
+    of a conv net (pyz_convnet_*), with MLPPlan's argument conventions.  x: (rows, H * W * C) float32, images row-major
+    (h, w, c)."""
+
+    def __init__(self, spec: ConvSpec, max_batch: int, max_particles: int = 1, device=None):
+        self.lib = _lib.load()
+        self.spec, self.max_batch, self.max_particles = spec, int(max_batch), int(max_particles)
+        if spec.loss == "bce":       # the conv net's loss kernels are the unfused k_loss_scce / k_loss_mse: no BinaryCrossentropy arm
+            raise ValueError("BinaryCrossentropy is not built for a conv model: use a softmax head with "
+                             "SparseCategoricalCrossentropy, or MeanSquaredError")
+        if spec.tail.dims[0] != spec.features:       # (also refuses a kernel or pool that does not fit, without a device)
+            raise ValueError(f"the Dense stack takes {spec.tail.dims[0]} inputs, the stem gives {spec.features} features")
+        ops = []
+        for op in spec.ops:
+            if op[0] == "conv":
+                if op[4] not in ("valid", "same"):
+                    raise ValueError(f"padding {op[4]!r} is neither 'valid' nor 'same'")
+                if op[5] == "softmax":
+                    raise ValueError("softmax is not an activation of a Conv2D here")
+                ops += [STEM_CONV, int(op[1]), int(op[2]), int(op[3]), 1 if op[4] == "same" else 0, ACT[op[5]]]
+            elif op[0] == "pool":
+                ops += [STEM_POOL, int(op[1]), int(op[2]), 0, 0, 0]
+            else:
+                raise ValueError(f"unknown stem op {op[0]!r}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("bayesian_inference_for_nn_amd needs an MI355X (no HIP device visible); there is no CPU path")
+        self.tail = MLPPlan(spec.tail, max_batch, max_particles, device)
+        self.device = self.tail.device
+        h = C.c_void_p()
+        H, W, Cin = spec.input_shape
+        with torch.cuda.device(self.device):
+            check(self.lib.pyz_stem_create(int(H), int(W), int(Cin), len(spec.ops), (C.c_int32 * len(ops))(*ops),
+                                           self.max_batch, self.max_particles, C.byref(h)))
+        self.h = h
+        self.D_stem = int(self.lib.pyz_stem_param_count(h))
+        self.F = int(self.lib.pyz_stem_feature_count(h))
+        self.D = self.D_stem + self.tail.D
+        assert self.D_stem == spec.stem_params and self.F == spec.features and self.D == spec.n_params
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.pyz_stem_destroy(self.h)
+            self.h = None
+        if getattr(self, "tail", None) is not None:
+            self.tail.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self):
+        return int(self.lib.pyz_stem_workspace_bytes(self.h)) + int(self.lib.pyz_mlp_workspace_bytes(self.tail.h))
+
+    def check_finite(self):
+        self.tail.check_finite()
+
+    # ------------------------------------------------------------------ helpers
+    def _check_xy(self, x, y, row_idx, batch):
+        _f32(x, name="x")
+        n_in = int(np.prod(self.spec.input_shape))
+        if x.dim() != 2 or x.shape[1] != n_in:
+            raise ValueError(f"x must be (rows, {n_in})")
+        n_rows = x.shape[0]
+        if row_idx is not None:
+            if row_idx.dtype != torch.int32 or not row_idx.is_cuda or not row_idx.is_contiguous():
+                raise TypeError("row_idx must be a contiguous CUDA int32 tensor")
+            if row_idx.numel() < batch:
+                raise ValueError("row_idx holds fewer entries than the batch")
+        elif batch > n_rows:
+            raise ValueError("batch exceeds the rows of x")
+        if y is not None:
+            if self.spec.loss == "scce":
+                if y.dtype != torch.int32 or not y.is_cuda or y.numel() != n_rows:
+                    raise TypeError("labels must be CUDA int32, one per row of x")
+            else:
+                _f32(y, name="y")
+                if y.numel() != n_rows * self.spec.dims[-1]:
+                    raise ValueError("targets must be (rows, out)")
+        if not (1 <= batch <= self.max_batch):
+            raise ValueError(f"batch {batch} outside [1, {self.max_batch}]")
+
+    def _particles(self, theta):
+        P = 1 if theta.dim() == 1 else int(theta.shape[0])
+        _f32(theta, name="theta")
+        if theta.numel() != P * self.D or not 1 <= P <= self.max_particles:
+            raise ValueError(f"theta must be ({self.D},) or (P <= {self.max_particles}, {self.D})")
+        return P
+
+    @staticmethod
+    def _batch(batch, x, row_idx):
+        return int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+
+    # ------------------------------------------------------------------ the stem alone
+    def stem_forward(self, theta, x, batch=None, row_idx=None, out=None):
+        """(P, batch, F) features (NHWC, flattened) of the stem's block of every row of theta (written to `out` if given)."""
+        P = self._particles(theta)
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, None, row_idx, batch)
+        if out is None:
+            out = torch.empty((P, batch, self.F), dtype=torch.float32, device=self.device)
+        _f32(out, (P, batch, self.F), "out")
+        check(self.lib.pyz_stem_forward(self.h, ptr(theta), self.D, P, ptr(x), ptr(row_idx), batch, ptr(out), _stream()))
+        return out
+
+    def stem_backward(self, theta, x, feature_grad, batch=None, row_idx=None):
+        """(P, D_stem): the stem's block of the gradient from d loss / d features (P, batch, F), after the stem_forward
+        of the same theta and batch."""
+        P = self._particles(theta)
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, None, row_idx, batch)
+        _f32(feature_grad, (P, batch, self.F), "feature_grad")
+        grad = torch.empty((P, self.D_stem), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_stem_backward(self.h, ptr(theta), self.D, P, ptr(x), ptr(row_idx), batch, ptr(feature_grad),
+                                         ptr(grad), self.D_stem, _stream()))
+        return grad
+
+    # ------------------------------------------------------------------ the whole net (MLPPlan's methods)
+    def forward(self, theta, x, batch=None, row_idx=None):
+        P = self._particles(theta)
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, None, row_idx, batch)
+        out = torch.empty((P, batch, self.spec.dims[-1]), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_convnet_forward(self.h, self.tail.h, ptr(theta), P, ptr(x), ptr(row_idx), batch, ptr(out),
+                                           _stream()))
+        return out
+
+    def loss_grad(self, theta, x, y, batch=None, row_idx=None, want_grad=True, grad_out=None):
+        P = self._particles(theta)
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, y, row_idx, batch)
+        grad = None
+        if want_grad:
+            grad = grad_out if grad_out is not None else torch.empty((P, self.D), dtype=torch.float32, device=self.device)
+            _f32(grad, (P, self.D), "grad_out")
+        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_convnet_loss_grad(self.h, self.tail.h, ptr(theta), P, ptr(x), ptr(y), ptr(row_idx), batch,
+                                             ptr(grad), ptr(loss), _stream()))
+        return loss, grad
+
+    def sgd_step(self, theta, x, y, lr, loss_out, batch=None, row_idx=None):
+        _f32(theta, (self.D,), "theta")
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, y, row_idx, batch)
+        check(self.lib.pyz_convnet_sgd_step(self.h, self.tail.h, ptr(theta), ptr(x), ptr(y), ptr(row_idx), batch, float(lr),
+                                            ptr(loss_out), _stream()))
+
+    def swag_step(self, theta, mean, sq_mean, dev_row, x, y, lr, n, update_moments, loss_out, batch=None, row_idx=None):
+        for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
+            _f32(t, (self.D,), nm)
+        if dev_row is not None:
+            _f32(dev_row, (self.D,), "dev_row")
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, y, row_idx, batch)
+        check(self.lib.pyz_convnet_swag_step(self.h, self.tail.h, ptr(theta), ptr(mean), ptr(sq_mean), ptr(dev_row), ptr(x),
+                                             ptr(y), ptr(row_idx), batch, float(lr), int(n), 1 if update_moments else 0,
+                                             ptr(loss_out), _stream()))
+
+    def _check_read_out(self, weights, x):
+        _f32(weights, name="weights")
+        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
+            raise ValueError(f"weights must be (draws >= 1, {self.D})")
+        self._check_xy(x, None, None, int(x.shape[0]) if x.dim() == 2 else 0)
+        return int(weights.shape[0]), int(x.shape[0]), self.spec.dims[-1]
+
+    def predict(self, weights, x, want_samples=True):
+        S, n, C_out = self._check_read_out(weights, x)
+        samples = torch.empty((S, n, C_out), dtype=torch.float32, device=self.device) if want_samples else None
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_convnet_predict(self.h, self.tail.h, ptr(weights), S, ptr(x), n, ptr(samples), ptr(mean), None,
+                                           _stream()))
+        return samples, mean
+
+    def predict_moments(self, weights, x):
+        S, n, C_out = self._check_read_out(weights, x)
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
+        m2 = torch.empty((n, C_out, C_out), dtype=torch.float32, device=self.device)
+        check(self.lib.pyz_convnet_predict(self.h, self.tail.h, ptr(weights), S, ptr(x), n, None, ptr(mean), ptr(m2),
+                                           _stream()))
+        return mean, m2
+
+
+def make_plan(spec, max_batch: int, max_particles: int = 1, device=None):
+    """The plan of a model's spec: a ConvPlan for a ConvSpec, else an MLPPlan."""
+    cls = ConvPlan if isinstance(spec, ConvSpec) else MLPPlan
+    return cls(spec, max_batch=max_batch, max_particles=max_particles, device=device)
+
+
 class PilcoPlan:
     """Owns one `pyz_pilco` handle: the policy update of Deep-PILCO (dynamics/deep_pilco.py:247-326) for a policy net
     `policy_spec` (dims (S, hidden..., A): a Dense-only MLPSpec, or a description with `dims`, `acts`, `n_params` and

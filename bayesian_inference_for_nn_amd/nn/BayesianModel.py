@@ -122,13 +122,29 @@ class BayesianModel:
         Bounds the activation workspace: rows x samples per launch (the plan keeps an activation and a delta buffer per
         layer: 2 * sum(widths) floats per (sample, row)).  2^29 floats = 2 GiB of the 288: 100 draws x 10 000 rows of the
         784 -> 200 -> 10 model go out as ONE launch per layer (3.35 ms for the wide layer against 7 x 0.61 ms in seven)."""
-        from ..engine import MLPPlan
+        from ..engine import make_plan
         rows = min(n, int(self._predict_rows_cap))
-        per = 2 * sum(int(d) for d in self._model.dims[1:])
+        per = 2 * sum(int(d) for d in self._model.dims[1:]) + self._stem_floats()
         chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
         if self._plan is None or self._plan.max_batch < rows or self._plan.max_particles < chunk_s:
-            self._plan = MLPPlan(self._model.spec, max_batch=rows, max_particles=chunk_s)
+            self._plan = make_plan(self._model.spec, max_batch=rows, max_particles=chunk_s)
         return rows
+
+    def _is_conv(self) -> bool:
+        return hasattr(self._model.spec, "ops")
+
+    def _stem_floats(self) -> int:
+        """Workspace floats per (draw, row) of a conv model's stem: an output and a delta map per op, and a pool's
+        winners (0 for a Dense model)."""
+        if not self._is_conv():
+            return 0
+        spec = self._model.spec
+        return sum((3 if op[0] == "pool" else 2) * o[0] * o[1] * o[2] for op, (_, o) in zip(spec.ops, spec.op_shapes()))
+
+    def _refuse_conv(self, what: str):
+        if self._is_conv():
+            raise ValueError(f"{what} is not built for a conv model (a model with Conv2D layers): an input gradient "
+                             "through the stem and surfaces over image space do not exist")
 
     def predict(self, x, nb_samples: int, y_true=None, loss_func=None):
         """(list of per-sample outputs, their mean); NaN outputs count as 0 (BayesianModel.py:106-129)."""
@@ -242,6 +258,7 @@ class BayesianModel:
         for the same draws); of each mean row q (one output: the pair (1 - m, m)) top = max q, cls = argmax q (int32),
         ent = -sum q log(q + 1e-5) in float32, raw; cols (nb_samples, n) = column `column` of every draw's prediction, or
         None.  Computed on the device by pyz_predict_surface: the sample tensor is neither written nor copied."""
+        self._refuse_conv("predictive_surface")
         import torch
         x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
         xd = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))).cuda()
@@ -254,6 +271,7 @@ class BayesianModel:
         workspace rule, each chunk's rows made on the device (pyz_grid_rows) and read out there (pyz_predict_surface):
         no grid row and no sample tensor reaches the host.  NumPy: cols (nb_samples, n1 * n2) or None, mean, top, cls,
         ent."""
+        self._refuse_conv("grid_surface")
         import torch
         from .. import engine
         basis = np.ascontiguousarray(np.asarray(basis, dtype=np.float32))
@@ -309,6 +327,7 @@ class BayesianModel:
         Robustness.adversarial_robustness (visualisations/Robustness.py:127-137), the sum over draws inside one device
         GEMM (pyz_input_grad).  loss: "scce" (y = integer labels), "mse" (y = targets) or "bce" (y = 0/1
         labels or targets in [0, 1], one per row)."""
+        self._refuse_conv("adversarial_examples")
         import torch
         from ..engine import MLPPlan, MLPSpec
         if loss not in ("scce", "mse", "bce"):

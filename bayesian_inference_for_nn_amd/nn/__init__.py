@@ -1,2 +1,2 @@
 from .BayesianModel import BayesianModel
-from .model import DenseNet, model_from_json, sequential_json
+from .model import ConvNet, DenseNet, conv_sequential_json, model_from_json, sequential_json

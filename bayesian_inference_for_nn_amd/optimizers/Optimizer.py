@@ -84,6 +84,7 @@ class Optimizer(ABC):
         if hasattr(model_config, "kinds"):
             raise ValueError("a network with an RBF layer is a Deep-PILCO policy only: an optimizer takes a Keras Sequential "
                              "JSON of Dense layers")
+        self._refuse_conv(model_config, kwargs.get("n_members"), dataset)
         if self.__compiled:
             raise Exception("Model Already compiled")
         else:
@@ -172,6 +173,24 @@ class Optimizer(ABC):
         """Hook: whether this optimizer's device-resident run takes the compiled model."""
         return False
 
+    # whether the class trains a model with a convolutional stem (SGD and SWAG do, one member, through step())
+    _conv_models = False
+
+    def _refuse_conv(self, model_config, n_members=None, dataset=None):
+        """compile(): a model with Conv2D layers is trained by SGD and SWAG with one member, on SparseCategoricalCrossentropy
+        or MeanSquaredError; everything else says so, before it reads a hyperparameter."""
+        from ..nn.model import is_conv_config
+        if not is_conv_config(model_config):
+            return
+        if dataset is not None and loss_kind(dataset._loss) == "bce":
+            raise ValueError(f"{type(self).__name__}: BinaryCrossentropy is not built for a model with Conv2D layers: use a "
+                             "softmax head with SparseCategoricalCrossentropy, or MeanSquaredError")
+        several = n_members is not None and int(n_members) != 1
+        if not self._conv_models or several:
+            raise ValueError(f"{type(self).__name__}" + (" with n_members > 1" if self._conv_models else "") +
+                             " does not take a model with Conv2D layers: conv models are trained by SGD and SWAG "
+                             "(one member)")
+
     def _fused_head(self) -> bool:
         """The chained SGD / SWAG / BBB / ADAM runs need the fused step: a last layer of at most 32 units."""
         return self._spec.dims[-1] <= 32
@@ -238,7 +257,7 @@ class Optimizer(ABC):
         ranks must draw one batch permutation and one particle initialisation."""
         import torch
         from .. import parallel
-        from ..engine import MLPPlan, MLPSpec
+        from ..engine import ConvSpec, MLPSpec, make_plan
         from ..nn.model import model_from_json
         self._rank, self._world = parallel.world_info()
         self._seed = parallel.shared_seed(seed) + (self._rank * int(chains_per_rank) if chain_per_rank else 0)
@@ -247,14 +266,18 @@ class Optimizer(ABC):
         self._net.reset_glorot(self._rng)
         self._loss_kind = loss_kind(self._dataset._loss)
         self._spec = MLPSpec(self._net.dims, self._net.acts, self._loss_kind)
+        self._conv = isinstance(self._net.spec, ConvSpec)
+        if self._conv:      # a stem in front of the Dense stack: the whole vector's spec, trained through a ConvPlan
+            self._refuse_conv(self._model_config, max_particles)
+            self._spec = ConvSpec(self._net.spec.input_shape, self._net.spec.ops, self._spec)
         x, y = self._dataset.training_dataset().as_numpy()
         self._training_dataset_cardinality = len(x)
         self._x_dev = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))).cuda()
         self._y_dev = self._labels_to_device(y)
         if full_batch:
             self._batch_size = len(x)
-        self._plan = MLPPlan(self._spec, max_batch=max(1, min(int(self._batch_size), len(x))),
-                             max_particles=max_particles)
+        self._plan = make_plan(self._spec, max_batch=max(1, min(int(self._batch_size), len(x))),
+                               max_particles=max_particles)
         self._D = self._plan.D
 
     def _labels_to_device(self, y):

@@ -21,6 +21,8 @@ from .Optimizer import DeviceScalar, Optimizer
 
 
 class SGD(Optimizer):
+    _conv_models = True      # a model with Conv2D layers trains through step(), one member
+
     def __init__(self):
         super().__init__()
         self._n = None
@@ -78,7 +80,7 @@ class SGD(Optimizer):
 
     # ------------------------------------------------------------------ quiet train(): device-resident runs
     def _resident_supported(self):
-        return self._n_members > 1 or self._fused_head()
+        return not self._conv and (self._n_members > 1 or self._fused_head())
 
     def _resident_launch(self, nb_iterations):
         lr, freq = float(self._lr), int(self._frequency)

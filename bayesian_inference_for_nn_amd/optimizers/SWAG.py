@@ -26,6 +26,8 @@ from .Optimizer import DeviceScalar, Optimizer
 
 
 class SWAG(Optimizer):
+    _conv_models = True      # a model with Conv2D layers trains through step(), one member
+
     def __init__(self):
         super().__init__()
         self._n = None
@@ -85,7 +87,7 @@ class SWAG(Optimizer):
 
     # ------------------------------------------------------------------ quiet train(): device-resident runs
     def _resident_supported(self):
-        return self._n_members > 1 or self._fused_head()
+        return not self._conv and (self._n_members > 1 or self._fused_head())
 
     def _resident_launch(self, nb_iterations):
         """The moment / deviation-column bookkeeping is a function of the step count and runs on the device (the chain

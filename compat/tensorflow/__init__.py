@@ -11,6 +11,7 @@ from bayesian_inference_for_nn_amd.nn.model import Array as Tensor
 from bayesian_inference_for_nn_amd.nn.model import DenseNet as _DenseNet
 from bayesian_inference_for_nn_amd.nn.model import model_from_json as _model_from_json
 from bayesian_inference_for_nn_amd.nn.model import sequential_json as _sequential_json
+from bayesian_inference_for_nn_amd.nn.model import conv_sequential_json as _conv_sequential_json
 
 __version__ = "2.15.0-pyz-standin"
 float32, float64, int32, int64 = np.float32, np.float64, np.int32, np.int64
@@ -45,6 +46,19 @@ class InputLayer(_Layer):
         self.input_shape = input_shape
 
 
+class Conv2D(_Layer):
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", activation=None, input_shape=None, **kw):
+        super().__init__(**kw)
+        self.filters, self.kernel_size, self.strides, self.padding = int(filters), kernel_size, strides, padding
+        self.activation, self.input_shape = _act_name(activation), input_shape
+
+
+class MaxPooling2D(_Layer):
+    def __init__(self, pool_size=(2, 2), strides=None, padding="valid", **kw):
+        super().__init__(**kw)
+        self.pool_size, self.strides, self.padding = pool_size, strides, padding
+
+
 class Sequential:
     """Collects layers and, once complete, behaves like the DenseNet built from its JSON."""
 
@@ -60,11 +74,22 @@ class Sequential:
 
     def _build(self) -> _DenseNet:
         if self._net is None:
-            shape, flatten, units, acts = None, False, [], []
+            shape, flatten, units, acts, stem = None, False, [], [], []
             for l in self._layers:
                 if getattr(l, "input_shape", None) is not None and shape is None:
                     shape = tuple(l.input_shape)
-                if isinstance(l, Flatten):
+                if isinstance(l, (Conv2D, MaxPooling2D)):
+                    # what the JSON builder cannot say (strides, a padded or overlapping pool) is not dropped silently
+                    if isinstance(l, Conv2D):
+                        if tuple(np.broadcast_to(l.strides, 2)) != (1, 1) or l.kw:
+                            raise ValueError(f"Conv2D: strides {l.strides} or arguments {sorted(l.kw)} are not supported")
+                        stem.append(("conv", l.filters, l.kernel_size, l.padding, l.activation))
+                    else:
+                        same = l.strides is None or tuple(np.broadcast_to(l.strides, 2)) == tuple(np.broadcast_to(l.pool_size, 2))
+                        if not same or l.padding != "valid" or l.kw:
+                            raise ValueError("MaxPooling2D: only strides equal to pool_size and padding 'valid' are supported")
+                        stem.append(("pool", l.pool_size))
+                elif isinstance(l, Flatten):
                     flatten = True
                 elif isinstance(l, Dense):
                     units.append(l.units)
@@ -74,7 +99,10 @@ class Sequential:
                                      "template for NNPolicy, not a model")
             if shape is None:
                 raise ValueError("the first layer needs input_shape")
-            self._net = _model_from_json(_sequential_json(shape, units, acts, flatten=flatten))
+            if stem:
+                self._net = _model_from_json(_conv_sequential_json(shape, stem, units, acts))
+            else:
+                self._net = _model_from_json(_sequential_json(shape, units, acts, flatten=flatten))
         return self._net
 
     def to_json(self):
@@ -153,7 +181,8 @@ keras = types.SimpleNamespace(
     Sequential=Sequential,
     Model=_DenseNet,
     models=types.SimpleNamespace(Sequential=Sequential, model_from_json=_model_from_json, Model=_DenseNet),
-    layers=types.SimpleNamespace(Dense=Dense, Flatten=Flatten, InputLayer=InputLayer),
+    layers=types.SimpleNamespace(Dense=Dense, Flatten=Flatten, InputLayer=InputLayer, Conv2D=Conv2D,
+                                 MaxPooling2D=MaxPooling2D),
     losses=types.SimpleNamespace(SparseCategoricalCrossentropy=_losses.SparseCategoricalCrossentropy,
                                  MeanSquaredError=_losses.MeanSquaredError,
                                  BinaryCrossentropy=_losses.BinaryCrossentropy),

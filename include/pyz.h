@@ -748,6 +748,56 @@ int pyz_debug_stamps(uint64_t *h_out, int64_t n_words);
  * when it is row = l / 16 + 4 r, column = l % 16). */
 int pyz_debug_mfma_f64_layout(int32_t *h_out512);
 
+/* ---- conv nets: a convolutional front end ("stem") in front of a Dense stack -------------------------------------------
+ * Keras Sequential [InputLayer] (Conv2D [MaxPooling2D])+ Flatten Dense+ as the reference's builder emits it
+ * (utils.py:129-150) and its image script trains it (tests/tf_dataset_test.py:42-57).  Images and feature maps are NHWC
+ * (channels_last), so Flatten is the identity on the buffer.  The flat vector holds, per Conv2D, the kernel
+ * (kh, kw, cin, cout) row-major then the bias (cout) -- Keras's variable order --, then the Dense layers as above:
+ * D_total = pyz_stem_param_count + pyz_mlp_param_count of the Dense plan, whose dims[0] is pyz_stem_feature_count and whose
+ * max_batch / max_particles are the stem's.
+ *
+ * h_ops holds 6 int32 per op: {PYZ_STEM_CONV, filters, kh, kw, padding (0 valid, 1 same), activation (linear .. sigmoid)}
+ * or {PYZ_STEM_POOL, ph, pw, 0, 0, 0}.  Strides and dilation are 1; `same` pads k - 1 in all, (k - 1) / 2 on top / left
+ * (TensorFlow's rule); a pool has stride = size, padding valid (floor(H / ph) rows, the remainder dropped) and follows a
+ * Conv2D; its winner is the first maximum in row-then-column order of the window, a NaN propagates.
+ * PYZ_E_INVALID for an unknown op or field, PYZ_E_SHAPE for a kernel larger than the padded image, a pool larger than its
+ * input, more than 4094 taps per filter or more than 2^24 output positions per launch -- all before a device is needed. */
+#define PYZ_STEM_CONV 0
+#define PYZ_STEM_POOL 1
+typedef struct pyz_stem pyz_stem;
+int pyz_stem_create(int in_h, int in_w, int in_c, int n_ops, const int32_t *h_ops, int max_batch, int max_particles,
+                    pyz_stem **out);
+int pyz_stem_destroy(pyz_stem *stem);
+int64_t pyz_stem_param_count(const pyz_stem *stem);
+int64_t pyz_stem_feature_count(const pyz_stem *stem);
+int64_t pyz_stem_workspace_bytes(const pyz_stem *stem);
+
+/* the stem alone: d_features (P, batch, F) from rows of d_x (images, H * W * C), particle p reading the stem's block at
+ * d_theta + p * theta_stride; and, after a forward of the same batch, the stem's block of the gradient (written at
+ * d_grad + p * grad_stride) from d_feature_grad (P, batch, F) = d loss / d features. */
+int pyz_stem_forward(pyz_stem *stem, const float *d_theta, int64_t theta_stride, int n_particles, const float *d_x,
+                     const int32_t *d_row_idx, int batch, float *d_features, void *stream);
+int pyz_stem_backward(pyz_stem *stem, const float *d_theta, int64_t theta_stride, int n_particles, const float *d_x,
+                      const int32_t *d_row_idx, int batch, const float *d_feature_grad, float *d_grad, int64_t grad_stride,
+                      void *stream);
+
+/* the whole net, d_theta (P, D_total): pyz_mlp_forward / pyz_mlp_loss_grad / pyz_sgd_step / pyz_swag_step / pyz_predict of
+ * a conv net (same arguments, same results).  The gradient of the whole vector is formed in one (D_total) buffer and the
+ * steps (one particle) run the unfused update kernels over it.  pyz_convnet_predict: d_m2 NULL = pyz_predict (d_samples
+ * optional); d_m2 given = pyz_predict_moments (d_samples ignored).  A Dense plan with PYZ_LOSS_BCE is refused by every one
+ * of them (PYZ_E_INVALID): BinaryCrossentropy is not built for conv nets. */
+int pyz_convnet_forward(pyz_stem *stem, pyz_mlp *dense, const float *d_theta, int n_particles, const float *d_x,
+                        const int32_t *d_row_idx, int batch, float *d_out, void *stream);
+int pyz_convnet_loss_grad(pyz_stem *stem, pyz_mlp *dense, const float *d_theta, int n_particles, const float *d_x,
+                          const void *d_y, const int32_t *d_row_idx, int batch, float *d_grad, float *d_loss, void *stream);
+int pyz_convnet_sgd_step(pyz_stem *stem, pyz_mlp *dense, float *d_theta, const float *d_x, const void *d_y,
+                         const int32_t *d_row_idx, int batch, float lr, float *d_loss, void *stream);
+int pyz_convnet_swag_step(pyz_stem *stem, pyz_mlp *dense, float *d_theta, float *d_mean, float *d_sq_mean, float *d_dev_row,
+                          const float *d_x, const void *d_y, const int32_t *d_row_idx, int batch, float lr, int64_t n,
+                          int update_moments, float *d_loss, void *stream);
+int pyz_convnet_predict(pyz_stem *stem, pyz_mlp *dense, const float *d_weights, int n_samples, const float *d_x, int n,
+                        float *d_samples, float *d_mean, float *d_m2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
