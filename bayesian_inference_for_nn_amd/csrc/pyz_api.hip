@@ -112,6 +112,30 @@ struct pyz_mlp_full : pyz_mlp {
   Extra x;
 };
 
+// A conv net: a stem (pyz_conv.h) in front of a Dense tail.
+struct StemOp {
+  int kind = 0;
+  int H = 0, W = 0, C = 0;         // input map
+  int OH = 0, OW = 0, N = 0;       // output map (a pool keeps C)
+  int kh = 0, kw = 0, pt = 0, pl = 0, act = 0;   // conv: kernel, top / left padding, activation; pool: kh x kw windows
+  int K = 0, KT = 0;               // conv: taps, and table entries (taps + bias, padded to even)
+  long long w_off = 0;
+  int2 *ktab = nullptr;
+  float *out = nullptr, *delta = nullptr;   // (max_p, max_batch, OH * OW * N) each
+  int32_t *win = nullptr;          // pool: the winners
+  long long size() const { return (long long)OH * OW * N; }
+};
+
+struct pyz_stem {
+  int n_ops = 0;
+  StemOp op[PYZ_STEM_MAX_OPS];
+  int in_h = 0, in_w = 0, in_c = 0, max_batch = 0, max_p = 0;
+  long long D = 0, F = 0;
+  size_t ws_bytes = 0;
+  float *part = nullptr;           // partial tiles of the weight gradients (stem_part_bytes)
+  bool forwarded = false;          // a forward has left every op's output in the workspace
+};
+
 namespace {
 
 inline pyz_mlp_full *full(pyz_mlp *m) { return static_cast<pyz_mlp_full *>(m); }
@@ -683,6 +707,268 @@ void launch_delta0(pyz_mlp *m, const float *theta, int P, const float *x, const 
   launch_bwd_data_hidden(m, theta, m->D, P, n, m->ctl, st);
 }
 
+// ---------------------------------------------------------------- conv nets: the stem's host side
+// rows of one range of the weight-gradient reduction: a function of the plan alone, so the split (and with it the order
+// of the sums) does not depend on the batch of the call
+inline int stem_rows_per_range(const pyz_stem *s, const StemOp &o) {
+  const long long m_max = (long long)s->max_batch * o.OH * o.OW;
+  return (int)std::max<long long>(256, ((m_max + 255) / 256 + 1) / 2 * 2);
+}
+
+int stem_check(const pyz_stem *s, int P, int batch) {
+  if (!s) return pyz_fail(PYZ_E_INVALID, "null stem");
+  if (batch <= 0 || batch > s->max_batch) return pyz_fail(PYZ_E_SHAPE, "batch %d outside [1, %d] of the plan", batch, s->max_batch);
+  if (P <= 0 || P > s->max_p) return pyz_fail(PYZ_E_SHAPE, "particle count %d outside [1, %d] of the plan", P, s->max_p);
+  return PYZ_OK;
+}
+
+ConvArgs conv_args(const pyz_stem *s, int o, const float *theta, long long theta_ps, const float *x, const int32_t *row_idx, int batch) {
+  const StemOp &c = s->op[o];
+  ConvArgs g{};
+  if (o == 0) {
+    g.in = x;
+    g.in_pstride = 0;
+    g.row_idx = row_idx;
+  } else {
+    g.in = s->op[o - 1].out;
+    g.in_pstride = (long long)s->max_batch * s->op[o - 1].size();
+  }
+  g.theta = theta;
+  g.theta_pstride = theta_ps;
+  g.w_off = c.w_off;
+  g.out = c.out;
+  g.out_pstride = (long long)s->max_batch * c.size();
+  g.delta = c.delta;
+  g.delta_pstride = g.out_pstride;
+  g.ktab = c.ktab;
+  g.batch = batch;
+  g.M = batch * c.OH * c.OW;
+  g.H = c.H; g.W = c.W; g.C = c.C; g.OH = c.OH; g.OW = c.OW; g.N = c.N; g.K = c.K; g.KT = c.KT;
+  g.kh = c.kh; g.kw = c.kw; g.pt = c.pt; g.pl = c.pl; g.act = c.act;
+  g.inv_ohw = 1.0f / (float)(c.OH * c.OW);
+  g.inv_ow = 1.0f / (float)c.OW;
+  return g;
+}
+
+PoolArgs pool_args(const pyz_stem *s, int o, int batch) {
+  const StemOp &q = s->op[o], &c = s->op[o - 1];
+  PoolArgs g{};
+  g.in = c.out;
+  g.in_pstride = (long long)s->max_batch * c.size();
+  g.out = q.out;
+  g.out_pstride = (long long)s->max_batch * q.size();
+  g.win = q.win;
+  g.dout = q.delta;
+  g.din = c.delta;
+  g.batch = batch;
+  g.H = q.H; g.W = q.W; g.C = q.C; g.OH = q.OH; g.OW = q.OW; g.ph = q.kh; g.pw = q.kw;
+  g.act_below = c.act;
+  return g;
+}
+
+inline int conv_waves(long long tiles, int steps) {
+  int S = 1;
+  while (S < PYZ_CONV_WAVES && tiles * S < 1024 && steps >= 16 * S) S *= 2;
+  return S;
+}
+
+// every op's output into the workspace; the last one's is the features (P, max_batch, F)
+void stem_forward(pyz_stem *s, const float *theta, long long theta_ps, int P, const float *x, const int32_t *row_idx, int batch,
+                  hipStream_t st) {
+  for (int o = 0; o < s->n_ops; ++o) {
+    const StemOp &c = s->op[o];
+    if (c.kind == PYZ_STEM_CONV) {
+      ConvArgs g = conv_args(s, o, theta, theta_ps, x, row_idx, batch);
+      const long long tiles = (long long)((g.M + 31) / 32) * ((g.N + 31) / 32);
+      const int S = conv_waves(tiles * P, g.KT / 2);
+      PYZ_LAUNCH(k_conv_fwd, dim3((unsigned)tiles, P), dim3(64 * S), (size_t)g.KT * 8 + (S > 1 ? S * 4096 : 0), st, g);
+    } else {
+      PoolArgs g = pool_args(s, o, batch);
+      PYZ_LAUNCH(k_pool_fwd, dim3((unsigned)cdiv((long long)batch * c.size(), 256), P), dim3(256), 0, st, g);
+    }
+  }
+  s->forwarded = true;
+}
+
+// bytes of the partial-tile slab of the weight-gradient reductions: the largest conv's (P, G, tiles, 32 x 32)
+size_t stem_part_bytes(const pyz_stem *s) {
+  size_t need = 0;
+  for (int o = 0; o < s->n_ops; ++o) {
+    const StemOp &c = s->op[o];
+    if (c.kind != PYZ_STEM_CONV) continue;
+    const long long tiles = (long long)((c.K + 1 + 31) / 32) * ((c.N + 31) / 32);
+    const long long G = cdiv((long long)s->max_batch * c.OH * c.OW, stem_rows_per_range(s, c));
+    need = std::max(need, sizeof(float) * (size_t)(s->max_p * G * tiles * 1024));
+  }
+  return need;
+}
+
+// the stem's block of the gradient from the last op's delta (a conv's: d loss / d pre-activation; a pool's: d loss / d out)
+void stem_backward(pyz_stem *s, const float *theta, long long theta_ps, int P, const float *x, const int32_t *row_idx, int batch,
+                   float *grad, long long grad_ps, hipStream_t st) {
+  for (int o = s->n_ops - 1; o >= 0; --o) {
+    const StemOp &c = s->op[o];
+    if (c.kind == PYZ_STEM_POOL) {
+      PoolArgs g = pool_args(s, o, batch);
+      PYZ_LAUNCH(k_pool_bwd, dim3((unsigned)cdiv((long long)batch * c.H * c.W * c.C, 256), P), dim3(256), 0, st, g);
+      continue;
+    }
+    ConvArgs g = conv_args(s, o, theta, theta_ps, x, row_idx, batch);
+    g.rows_per_g = stem_rows_per_range(s, c);
+    g.G = cdiv(g.M, g.rows_per_g);
+    g.part = s->part;
+    g.grad = grad;
+    g.grad_pstride = grad_ps;
+    const long long tiles = (long long)((g.K + 1 + 31) / 32) * ((g.N + 31) / 32);
+    const int S = conv_waves(tiles * g.G * P, std::min(g.M, g.rows_per_g) / 2);
+    PYZ_LAUNCH(k_conv_wgrad, dim3((unsigned)(tiles * g.G), P), dim3(64 * S), (S > 1 ? S * 4096 : 0) + PYZ_WGRAD_CHUNK * 16, st, g);
+    PYZ_LAUNCH(k_conv_wgrad_reduce, dim3((unsigned)cdiv((long long)(g.K + 1) * g.N, 16), P), dim3(256), 0, st, g);
+    if (o > 0) {   // (not launched for the first conv: nothing is below it)
+      const StemOp &b = s->op[o - 1];
+      g.out = b.delta;
+      g.out_pstride = (long long)s->max_batch * b.size();
+      g.below = b.kind == PYZ_STEM_CONV ? b.out : nullptr;
+      g.below_pstride = g.out_pstride;
+      g.act_below = b.act;
+      PYZ_LAUNCH(k_conv_dgrad, dim3((unsigned)cdiv((long long)batch * c.H * c.W * c.C, 256), P), dim3(256), 0, st, g);
+    }
+  }
+}
+
+int convnet_check(const pyz_stem *s, const pyz_mlp *m, int P, int batch) {
+  int rc = stem_check(s, P, batch);
+  if (rc) return rc;
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  // the conv net's loss goes through launch_loss (k_loss_scce / k_loss_mse), which has no BinaryCrossentropy arm: on a Dense
+  // net that loss always takes the fused head (one output unit)
+  if (m->loss == PYZ_LOSS_BCE) return pyz_fail(PYZ_E_INVALID, "BinaryCrossentropy is not built for a conv net: use a softmax head with SparseCategoricalCrossentropy, or MeanSquaredError");
+  if (m->dims[0] != s->F || m->max_batch != s->max_batch || m->max_p != s->max_p)
+    return pyz_fail(PYZ_E_INVALID, "the Dense plan (input %d, max_batch %d, max_particles %d) does not continue the stem (%lld features, %d, %d)",
+                    m->dims[0], m->max_batch, m->max_p, s->F, s->max_batch, s->max_p);
+  return PYZ_OK;
+}
+
+inline const float *stem_features(const pyz_stem *s) { return s->op[s->n_ops - 1].out; }
+
+// stem + Dense forward over the Dense layers [0, l_end) (all of them by default); the Dense outputs land in m->act
+void convnet_forward(pyz_stem *s, pyz_mlp *m, const float *theta, int P, const float *x, const int32_t *row_idx, int batch,
+                     hipStream_t st, int l_end = -1) {
+  const long long Dt = s->D + m->D;
+  stem_forward(s, theta, Dt, P, x, row_idx, batch, st);
+  launch_forward(m, theta + s->D, Dt, P, stem_features(s), nullptr, batch, m->ctl, st, nullptr, l_end, nullptr, 0,
+                 (long long)s->max_batch * s->F);
+}
+
+// forward, loss and (grad != null) the gradient of the whole vector into grad (P, D_total).  The callers have set the plan's
+// ctl with set_ctl(..., row_off = 0, ...), and that zero matters: the stem's kernels read row_idx[b] as it stands, k_loss_*
+// read row_idx[ctl->row_off + m] -- the images and the labels are the same rows only while row_off is 0 (a chained run,
+// which moves row_off, would have to hand the stem row_idx + row_off)
+int convnet_loss_backward(pyz_stem *s, pyz_mlp *m, const float *theta, int P, const float *x, const void *y,
+                          const int32_t *row_idx, int batch, float *grad, hipStream_t st) {
+  const long long Dt = s->D + m->D;
+  convnet_forward(s, m, theta, P, x, row_idx, batch, st);
+  launch_loss(m, P, y, row_idx, batch, m->ctl, grad != nullptr, st);   // the labels go through row_idx; the features are in batch order
+  m->cur_nblk = loss_nblk(m, batch);
+  if (!grad) return PYZ_OK;
+  const StemOp &last = s->op[s->n_ops - 1];
+  // (nothing has updated a weight by the time the feature gradient reads layer 0's: the updates are the callers' last launch)
+  const TailOf tail{(long long)s->max_batch * s->F, Dt, last.delta, last.kind == PYZ_STEM_CONV ? last.act : PYZ_ACT_LINEAR};
+  launch_backward(m, theta + s->D, Dt, P, stem_features(s), nullptr, batch, m->ctl, grad + s->D, st, nullptr, &tail);
+  stem_backward(s, theta, Dt, P, x, row_idx, batch, grad, Dt, st);
+  return PYZ_OK;
+}
+
+// ---------------------------------------------------------------- what the forward and read-out entries share
+// A Dense model (s == nullptr) or a conv stem in front of a Dense tail.
+struct Net {
+  pyz_stem *s;
+  pyz_mlp *m;
+  long long D() const { return s ? s->D + m->D : m->D; }   // one row of weights
+  // the forward of P rows of weights, stopping before Dense layer `upto` (all layers by default); outputs land in m->act
+  void forward(const float *theta, int P, const float *x, const int32_t *row_idx, int batch, hipStream_t st, int upto = -1) const {
+    if (s)
+      convnet_forward(s, m, theta, P, x, row_idx, batch, st, upto);
+    else
+      launch_forward(m, theta, m->D, P, x, row_idx, batch, m->ctl, st, nullptr, upto);
+  }
+};
+
+// The walk of every read-out over its draws, `chunk` rows of weights at a time: the forward of a chunk on the n rows of x (up
+// to Dense layer `upto`; none with do_forward = false, where the epilogue runs a forward of its own), then
+// epilogue(s0, S, weights of the chunk) -> code.  The caller has set the plan's ctl for n rows.
+template <class Epilogue>
+int for_draw_chunks(const Net &net, const float *weights, int n_samples, const float *x, int n, int chunk, hipStream_t st,
+                    Epilogue &&epilogue, bool do_forward = true, int upto = -1) {
+  for (int s0 = 0; s0 < n_samples; s0 += chunk) {
+    const int S = std::min(chunk, n_samples - s0);
+    const float *w = weights + (long long)s0 * net.D();
+    if (do_forward) net.forward(w, S, x, nullptr, n, st, upto);
+    const int rc = epilogue(s0, S, w);
+    if (rc) return rc;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// pyz_mlp_forward / pyz_convnet_forward behind their plan checks
+int net_forward(const Net &net, const float *d_theta, int P, const float *d_x, const int32_t *d_row_idx, int batch,
+                float *d_out, void *stream) {
+  pyz_mlp *m = net.m;
+  if (!d_theta || !d_x || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
+  hipStream_t st = as_stream(stream);
+  int rc = set_ctl(m, 0, batch, 0.0f, 0, 0, 0, st);
+  if (rc) return rc;
+  net.forward(d_theta, P, d_x, d_row_idx, batch, st);
+  const int C = m->dims[m->L];
+  PYZ_LAUNCH(k_forward_finish, dim3(cdiv(batch, 256), P), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C,
+             m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0, batch, d_out);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// pyz_predict / pyz_convnet_predict (d_m2 == null) behind their argument checks
+int net_predict(const Net &net, const float *d_weights, int n_samples, const float *d_x, int n, float *d_samples,
+                float *d_mean, void *stream) {
+  pyz_mlp *m = net.m;
+  hipStream_t st = as_stream(stream);
+  int rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st);
+  if (rc) return rc;
+  const int C = m->dims[m->L];
+  const int softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
+  return for_draw_chunks(net, d_weights, n_samples, d_x, n, m->max_p, st, [&](int s0, int S, const float *) {
+    PYZ_LAUNCH(k_predict_rows, dim3(cdiv(n, 256), S), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C,
+               softmax, n, d_samples ? d_samples + (long long)s0 * n * C : nullptr);
+    PYZ_LAUNCH(k_predict_mean, dim3((unsigned)cdiv((long long)n * C, 256)), dim3(256), 0, st, m->act[m->L - 1],
+               (long long)m->max_batch * C, (long long)n * C, S, d_mean, s0 > 0 ? 1 : 0, 1.0f / (float)n_samples);
+    return PYZ_OK;
+  });
+}
+
+// pyz_predict_moments / pyz_convnet_predict (d_m2 != null) behind their argument checks
+int net_predict_moments(const Net &net, const float *d_weights, int n_samples, const float *d_x, int n, float *d_mean,
+                        float *d_m2, void *stream) {
+  pyz_mlp *m = net.m;
+  hipStream_t st = as_stream(stream);
+  int rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st);
+  if (rc) return rc;
+  PredictMomentsArgs g{};
+  g.last = m->act[m->L - 1];
+  g.C = m->dims[m->L];
+  g.pstride = (long long)m->max_batch * g.C;
+  g.softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
+  g.n = n;
+  g.mean = d_mean;
+  g.m2 = d_m2;
+  g.inv_total = 1.0f / (float)n_samples;
+  return for_draw_chunks(net, d_weights, n_samples, d_x, n, m->max_p, st, [&](int s0, int S, const float *) {
+    g.S = S;
+    g.accumulate = s0 > 0 ? 1 : 0;
+    if (!pyz_launch_predict_moments(g, st))
+      return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the moments kernel's LDS", g.C);
+    return PYZ_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -843,15 +1129,7 @@ int pyz_mlp_forward(pyz_mlp *m, const float *d_theta, int P, const float *d_x, c
                     float *d_out, void *stream) {
   int rc = check_call(m, P, batch);
   if (rc) return rc;
-  if (!d_theta || !d_x || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
-  hipStream_t st = as_stream(stream);
-  if ((rc = set_ctl(m, 0, batch, 0.0f, 0, 0, 0, st))) return rc;
-  launch_forward(m, d_theta, m->D, P, d_x, d_row_idx, batch, m->ctl, st);
-  const int C = m->dims[m->L];
-  PYZ_LAUNCH(k_forward_finish, dim3(cdiv(batch, 256), P), dim3(256), 0, st, m->act[m->L - 1],
-                     (long long)m->max_batch * C, C, m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0, batch, d_out);
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  return net_forward(Net{nullptr, m}, d_theta, P, d_x, d_row_idx, batch, d_out, stream);
 }
 
 // ---------------------------------------------------------------- G1-G3
@@ -1880,27 +2158,24 @@ int pyz_lane_scores(pyz_mlp *m, const float *d_weights, int n_lanes, const float
   g.part = ws;
   g.epart = ws + words;
   g.ticket = reinterpret_cast<unsigned *>(ws + 2 * words);
-  for (int s0 = 0; s0 < n_lanes; s0 += m->max_p) {
-    const int S = std::min(m->max_p, n_lanes - s0);
-    const float *w = d_weights + (long long)s0 * m->D;
-    launch_forward(m, w, m->D, S, d_x, nullptr, n, m->ctl, st, nullptr, L - 1);
-    {   // the last layer: launch_forward's launch, the activation left off where the head takes the logit
-      DenseArgs f = forward_args(m, L - 1, w, m->D, d_x, nullptr, m->ctl, nullptr);
-      if (m->loss == PYZ_LOSS_BCE) f.act = PYZ_ACT_LINEAR;
-      f.wt = pyz_wt_for(S);
-      if (!pyz_launch_fwd_ring(f, n, S, st)) {
-        if (!f.row_idx && !f.init_on && !f.gather_out) f.rows_cap = std::min(n, m->max_batch);
-        pyz_launch_fwd(f, n, S, st);
-      }
+  // the forward stops before the last layer: that one is launch_forward's launch with the activation left off where the
+  // head takes the logit
+  rc = for_draw_chunks(Net{nullptr, m}, d_weights, n_lanes, d_x, n, m->max_p, st, [&](int s0, int S, const float *w) {
+    DenseArgs f = forward_args(m, L - 1, w, m->D, d_x, nullptr, m->ctl, nullptr);
+    if (m->loss == PYZ_LOSS_BCE) f.act = PYZ_ACT_LINEAR;
+    f.wt = pyz_wt_for(S);
+    if (!pyz_launch_fwd_ring(f, n, S, st)) {
+      if (!f.row_idx && !f.init_on && !f.gather_out) f.rows_cap = std::min(n, m->max_batch);
+      pyz_launch_fwd(f, n, S, st);
     }
     PYZ_HIP(hipMemsetAsync(g.ticket, 0, sizeof(unsigned) * (size_t)S, st));
     g.loss_sum = d_loss_sum + s0;
     g.errors = d_errors ? reinterpret_cast<long long *>(d_errors) + s0 : nullptr;
     PYZ_LAUNCH(k_lane_scores, dim3((unsigned)nblk, (unsigned)S), dim3(256), 0, st, g);
-  }
-  PYZ_HIP(hipFreeAsync(ws, st));
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+    return PYZ_OK;
+  }, true, L - 1);
+  PYZ_HIP(hipFreeAsync(ws, st));   // (also after a failed chunk: the scratch is not left behind)
+  return rc;
 }
 
 // The SGD train loop (SGD.py:42-69 inside Optimizer.py:121-134) as one device-resident run: the launch sequence
@@ -3095,21 +3370,7 @@ int pyz_predict(pyz_mlp *m, const float *d_weights, int n_samples, const float *
   if (n_samples <= 0 || n <= 0) return pyz_fail(PYZ_E_INVALID, "n_samples and n must be positive");
   if (n > m->max_batch) return pyz_fail(PYZ_E_SHAPE, "n %d exceeds the plan's max_batch %d", n, m->max_batch);
   if (!d_weights || !d_x || !d_mean) return pyz_fail(PYZ_E_INVALID, "null device pointer");
-  hipStream_t st = as_stream(stream);
-  int rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st);
-  if (rc) return rc;
-  const int C = m->dims[m->L];
-  const int softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
-  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
-    const int S = std::min(m->max_p, n_samples - s0);
-    launch_forward(m, d_weights + (long long)s0 * m->D, m->D, S, d_x, nullptr, n, m->ctl, st);
-    PYZ_LAUNCH(k_predict_rows, dim3(cdiv(n, 256), S), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C,
-               softmax, n, d_samples ? d_samples + (long long)s0 * n * C : nullptr);
-    PYZ_LAUNCH(k_predict_mean, dim3((unsigned)cdiv((long long)n * C, 256)), dim3(256), 0, st, m->act[m->L - 1],
-               (long long)m->max_batch * C, (long long)n * C, S, d_mean, s0 > 0 ? 1 : 0, 1.0f / (float)n_samples);
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  return net_predict(Net{nullptr, m}, d_weights, n_samples, d_x, n, d_samples, d_mean, stream);
 }
 
 int pyz_predict_moments(pyz_mlp *m, const float *d_weights, int n_samples, const float *d_x, int n, float *d_mean,
@@ -3118,27 +3379,7 @@ int pyz_predict_moments(pyz_mlp *m, const float *d_weights, int n_samples, const
   if (n_samples <= 0 || n <= 0) return pyz_fail(PYZ_E_INVALID, "n_samples and n must be positive");
   if (n > m->max_batch) return pyz_fail(PYZ_E_SHAPE, "n %d exceeds the plan's max_batch %d", n, m->max_batch);
   if (!d_weights || !d_x || !d_mean || !d_m2) return pyz_fail(PYZ_E_INVALID, "null device pointer");
-  hipStream_t st = as_stream(stream);
-  int rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st);
-  if (rc) return rc;
-  PredictMomentsArgs g{};
-  g.last = m->act[m->L - 1];
-  g.C = m->dims[m->L];
-  g.pstride = (long long)m->max_batch * g.C;
-  g.softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
-  g.n = n;
-  g.mean = d_mean;
-  g.m2 = d_m2;
-  g.inv_total = 1.0f / (float)n_samples;
-  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
-    g.S = std::min(m->max_p, n_samples - s0);
-    g.accumulate = s0 > 0 ? 1 : 0;
-    launch_forward(m, d_weights + (long long)s0 * m->D, m->D, g.S, d_x, nullptr, n, m->ctl, st);
-    if (!pyz_launch_predict_moments(g, st))
-      return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the moments kernel's LDS", g.C);
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  return net_predict_moments(Net{nullptr, m}, d_weights, n_samples, d_x, n, d_mean, d_m2, stream);
 }
 
 // ---------------------------------------------------------------- decision surfaces (Plotter)
@@ -3181,17 +3422,15 @@ int pyz_predict_surface(pyz_mlp *m, const float *d_weights, int n_samples, const
   g.cls = d_cls;
   g.ent = d_ent;
   g.inv_total = 1.0f / (float)n_samples;
-  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
-    g.S = std::min(m->max_p, n_samples - s0);
+  return for_draw_chunks(Net{nullptr, m}, d_weights, n_samples, d_x, n, m->max_p, st, [&](int s0, int S, const float *) {
+    g.S = S;
     g.accumulate = s0 > 0 ? 1 : 0;
-    g.finish = s0 + g.S >= n_samples && (d_top || d_cls || d_ent) ? 1 : 0;
+    g.finish = s0 + S >= n_samples && (d_top || d_cls || d_ent) ? 1 : 0;
     g.cols = d_cols ? d_cols + (long long)s0 * n : nullptr;
-    launch_forward(m, d_weights + (long long)s0 * m->D, m->D, g.S, d_x, nullptr, n, m->ctl, st);
     if (!pyz_launch_predict_surface(g, st))
       return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the surface kernel's LDS", g.C);
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+    return PYZ_OK;
+  });
 }
 
 // ---------------------------------------------------------------- R2
@@ -3208,9 +3447,8 @@ int pyz_input_grad(pyz_mlp *m, const float *d_weights, int n_samples, const floa
   m->grad_owner = 2;   // (the losses of a call without d_loss land in m->scal)
   const int N = m->dims[1];
   const int chunk = std::min(m->max_p, pyz_input_grad_max_draws(N));
-  for (int s0 = 0; s0 < n_samples; s0 += chunk) {
-    const int P = std::min(chunk, n_samples - s0);
-    const float *theta = d_weights + (long long)s0 * m->D;
+  // (no forward from the walk: launch_delta0 runs the one its head needs)
+  return for_draw_chunks(Net{nullptr, m}, d_weights, n_samples, d_x, n, chunk, st, [&](int s0, int P, const float *theta) {
     launch_delta0(m, theta, P, d_x, d_y, n, st);
     PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, m->ctl, d_loss ? d_loss + s0 : m->scal,
                m->nonfinite);
@@ -3234,9 +3472,8 @@ int pyz_input_grad(pyz_mlp *m, const float *d_weights, int n_samples, const floa
       g.eps = epsilon;
     }
     pyz_launch_input_grad(g, st);
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+    return PYZ_OK;
+  }, false);
 }
 
 // ---------------------------------------------------------------- noise
@@ -3772,208 +4009,7 @@ int pyz_debug_stamps(uint64_t *h_out, int64_t n_words) {
 #endif
 }
 
-}  // extern "C"
-
 // ---------------------------------------------------------------- conv nets: a stem (pyz_conv.h) in front of a Dense tail
-struct StemOp {
-  int kind = 0;
-  int H = 0, W = 0, C = 0;         // input map
-  int OH = 0, OW = 0, N = 0;       // output map (a pool keeps C)
-  int kh = 0, kw = 0, pt = 0, pl = 0, act = 0;   // conv: kernel, top / left padding, activation; pool: kh x kw windows
-  int K = 0, KT = 0;               // conv: taps, and table entries (taps + bias, padded to even)
-  long long w_off = 0;
-  int2 *ktab = nullptr;
-  float *out = nullptr, *delta = nullptr;   // (max_p, max_batch, OH * OW * N) each
-  int32_t *win = nullptr;          // pool: the winners
-  long long size() const { return (long long)OH * OW * N; }
-};
-
-struct pyz_stem {
-  int n_ops = 0;
-  StemOp op[PYZ_STEM_MAX_OPS];
-  int in_h = 0, in_w = 0, in_c = 0, max_batch = 0, max_p = 0;
-  long long D = 0, F = 0;
-  size_t ws_bytes = 0;
-  float *part = nullptr;           // partial tiles of the weight gradients (stem_part_bytes)
-  bool forwarded = false;          // a forward has left every op's output in the workspace
-};
-
-namespace {
-
-// rows of one range of the weight-gradient reduction: a function of the plan alone, so the split (and with it the order
-// of the sums) does not depend on the batch of the call
-inline int stem_rows_per_range(const pyz_stem *s, const StemOp &o) {
-  const long long m_max = (long long)s->max_batch * o.OH * o.OW;
-  return (int)std::max<long long>(256, ((m_max + 255) / 256 + 1) / 2 * 2);
-}
-
-int stem_check(const pyz_stem *s, int P, int batch) {
-  if (!s) return pyz_fail(PYZ_E_INVALID, "null stem");
-  if (batch <= 0 || batch > s->max_batch) return pyz_fail(PYZ_E_SHAPE, "batch %d outside [1, %d] of the plan", batch, s->max_batch);
-  if (P <= 0 || P > s->max_p) return pyz_fail(PYZ_E_SHAPE, "particle count %d outside [1, %d] of the plan", P, s->max_p);
-  return PYZ_OK;
-}
-
-ConvArgs conv_args(const pyz_stem *s, int o, const float *theta, long long theta_ps, const float *x, const int32_t *row_idx, int batch) {
-  const StemOp &c = s->op[o];
-  ConvArgs g{};
-  if (o == 0) {
-    g.in = x;
-    g.in_pstride = 0;
-    g.row_idx = row_idx;
-  } else {
-    g.in = s->op[o - 1].out;
-    g.in_pstride = (long long)s->max_batch * s->op[o - 1].size();
-  }
-  g.theta = theta;
-  g.theta_pstride = theta_ps;
-  g.w_off = c.w_off;
-  g.out = c.out;
-  g.out_pstride = (long long)s->max_batch * c.size();
-  g.delta = c.delta;
-  g.delta_pstride = g.out_pstride;
-  g.ktab = c.ktab;
-  g.batch = batch;
-  g.M = batch * c.OH * c.OW;
-  g.H = c.H; g.W = c.W; g.C = c.C; g.OH = c.OH; g.OW = c.OW; g.N = c.N; g.K = c.K; g.KT = c.KT;
-  g.kh = c.kh; g.kw = c.kw; g.pt = c.pt; g.pl = c.pl; g.act = c.act;
-  g.inv_ohw = 1.0f / (float)(c.OH * c.OW);
-  g.inv_ow = 1.0f / (float)c.OW;
-  return g;
-}
-
-PoolArgs pool_args(const pyz_stem *s, int o, int batch) {
-  const StemOp &q = s->op[o], &c = s->op[o - 1];
-  PoolArgs g{};
-  g.in = c.out;
-  g.in_pstride = (long long)s->max_batch * c.size();
-  g.out = q.out;
-  g.out_pstride = (long long)s->max_batch * q.size();
-  g.win = q.win;
-  g.dout = q.delta;
-  g.din = c.delta;
-  g.batch = batch;
-  g.H = q.H; g.W = q.W; g.C = q.C; g.OH = q.OH; g.OW = q.OW; g.ph = q.kh; g.pw = q.kw;
-  g.act_below = c.act;
-  return g;
-}
-
-inline int conv_waves(long long tiles, int steps) {
-  int S = 1;
-  while (S < PYZ_CONV_WAVES && tiles * S < 1024 && steps >= 16 * S) S *= 2;
-  return S;
-}
-
-// every op's output into the workspace; the last one's is the features (P, max_batch, F)
-void stem_forward(pyz_stem *s, const float *theta, long long theta_ps, int P, const float *x, const int32_t *row_idx, int batch,
-                  hipStream_t st) {
-  for (int o = 0; o < s->n_ops; ++o) {
-    const StemOp &c = s->op[o];
-    if (c.kind == PYZ_STEM_CONV) {
-      ConvArgs g = conv_args(s, o, theta, theta_ps, x, row_idx, batch);
-      const long long tiles = (long long)((g.M + 31) / 32) * ((g.N + 31) / 32);
-      const int S = conv_waves(tiles * P, g.KT / 2);
-      PYZ_LAUNCH(k_conv_fwd, dim3((unsigned)tiles, P), dim3(64 * S), (size_t)g.KT * 8 + (S > 1 ? S * 4096 : 0), st, g);
-    } else {
-      PoolArgs g = pool_args(s, o, batch);
-      PYZ_LAUNCH(k_pool_fwd, dim3((unsigned)cdiv((long long)batch * c.size(), 256), P), dim3(256), 0, st, g);
-    }
-  }
-  s->forwarded = true;
-}
-
-// bytes of the partial-tile slab of the weight-gradient reductions: the largest conv's (P, G, tiles, 32 x 32)
-size_t stem_part_bytes(const pyz_stem *s) {
-  size_t need = 0;
-  for (int o = 0; o < s->n_ops; ++o) {
-    const StemOp &c = s->op[o];
-    if (c.kind != PYZ_STEM_CONV) continue;
-    const long long tiles = (long long)((c.K + 1 + 31) / 32) * ((c.N + 31) / 32);
-    const long long G = cdiv((long long)s->max_batch * c.OH * c.OW, stem_rows_per_range(s, c));
-    need = std::max(need, sizeof(float) * (size_t)(s->max_p * G * tiles * 1024));
-  }
-  return need;
-}
-
-// the stem's block of the gradient from the last op's delta (a conv's: d loss / d pre-activation; a pool's: d loss / d out)
-void stem_backward(pyz_stem *s, const float *theta, long long theta_ps, int P, const float *x, const int32_t *row_idx, int batch,
-                   float *grad, long long grad_ps, hipStream_t st) {
-  for (int o = s->n_ops - 1; o >= 0; --o) {
-    const StemOp &c = s->op[o];
-    if (c.kind == PYZ_STEM_POOL) {
-      PoolArgs g = pool_args(s, o, batch);
-      PYZ_LAUNCH(k_pool_bwd, dim3((unsigned)cdiv((long long)batch * c.H * c.W * c.C, 256), P), dim3(256), 0, st, g);
-      continue;
-    }
-    ConvArgs g = conv_args(s, o, theta, theta_ps, x, row_idx, batch);
-    g.rows_per_g = stem_rows_per_range(s, c);
-    g.G = cdiv(g.M, g.rows_per_g);
-    g.part = s->part;
-    g.grad = grad;
-    g.grad_pstride = grad_ps;
-    const long long tiles = (long long)((g.K + 1 + 31) / 32) * ((g.N + 31) / 32);
-    const int S = conv_waves(tiles * g.G * P, std::min(g.M, g.rows_per_g) / 2);
-    PYZ_LAUNCH(k_conv_wgrad, dim3((unsigned)(tiles * g.G), P), dim3(64 * S), (S > 1 ? S * 4096 : 0) + PYZ_WGRAD_CHUNK * 16, st, g);
-    PYZ_LAUNCH(k_conv_wgrad_reduce, dim3((unsigned)cdiv((long long)(g.K + 1) * g.N, 16), P), dim3(256), 0, st, g);
-    if (o > 0) {   // (not launched for the first conv: nothing is below it)
-      const StemOp &b = s->op[o - 1];
-      g.out = b.delta;
-      g.out_pstride = (long long)s->max_batch * b.size();
-      g.below = b.kind == PYZ_STEM_CONV ? b.out : nullptr;
-      g.below_pstride = g.out_pstride;
-      g.act_below = b.act;
-      PYZ_LAUNCH(k_conv_dgrad, dim3((unsigned)cdiv((long long)batch * c.H * c.W * c.C, 256), P), dim3(256), 0, st, g);
-    }
-  }
-}
-
-int convnet_check(const pyz_stem *s, const pyz_mlp *m, int P, int batch) {
-  int rc = stem_check(s, P, batch);
-  if (rc) return rc;
-  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
-  // the conv net's loss goes through launch_loss (k_loss_scce / k_loss_mse), which has no BinaryCrossentropy arm: on a Dense
-  // net that loss always takes the fused head (one output unit)
-  if (m->loss == PYZ_LOSS_BCE) return pyz_fail(PYZ_E_INVALID, "BinaryCrossentropy is not built for a conv net: use a softmax head with SparseCategoricalCrossentropy, or MeanSquaredError");
-  if (m->dims[0] != s->F || m->max_batch != s->max_batch || m->max_p != s->max_p)
-    return pyz_fail(PYZ_E_INVALID, "the Dense plan (input %d, max_batch %d, max_particles %d) does not continue the stem (%lld features, %d, %d)",
-                    m->dims[0], m->max_batch, m->max_p, s->F, s->max_batch, s->max_p);
-  return PYZ_OK;
-}
-
-inline const float *stem_features(const pyz_stem *s) { return s->op[s->n_ops - 1].out; }
-
-// stem + Dense forward; the Dense outputs land in m->act
-void convnet_forward(pyz_stem *s, pyz_mlp *m, const float *theta, int P, const float *x, const int32_t *row_idx, int batch,
-                     hipStream_t st) {
-  const long long Dt = s->D + m->D;
-  stem_forward(s, theta, Dt, P, x, row_idx, batch, st);
-  launch_forward(m, theta + s->D, Dt, P, stem_features(s), nullptr, batch, m->ctl, st, nullptr, -1, nullptr, 0,
-                 (long long)s->max_batch * s->F);
-}
-
-// forward, loss and (grad != null) the gradient of the whole vector into grad (P, D_total).  The callers have set the plan's
-// ctl with set_ctl(..., row_off = 0, ...), and that zero matters: the stem's kernels read row_idx[b] as it stands, k_loss_*
-// read row_idx[ctl->row_off + m] -- the images and the labels are the same rows only while row_off is 0 (a chained run,
-// which moves row_off, would have to hand the stem row_idx + row_off)
-int convnet_loss_backward(pyz_stem *s, pyz_mlp *m, const float *theta, int P, const float *x, const void *y,
-                          const int32_t *row_idx, int batch, float *grad, hipStream_t st) {
-  const long long Dt = s->D + m->D;
-  convnet_forward(s, m, theta, P, x, row_idx, batch, st);
-  launch_loss(m, P, y, row_idx, batch, m->ctl, grad != nullptr, st);   // the labels go through row_idx; the features are in batch order
-  m->cur_nblk = loss_nblk(m, batch);
-  if (!grad) return PYZ_OK;
-  const StemOp &last = s->op[s->n_ops - 1];
-  // (nothing has updated a weight by the time the feature gradient reads layer 0's: the updates are the callers' last launch)
-  const TailOf tail{(long long)s->max_batch * s->F, Dt, last.delta, last.kind == PYZ_STEM_CONV ? last.act : PYZ_ACT_LINEAR};
-  launch_backward(m, theta + s->D, Dt, P, stem_features(s), nullptr, batch, m->ctl, grad + s->D, st, nullptr, &tail);
-  stem_backward(s, theta, Dt, P, x, row_idx, batch, grad, Dt, st);
-  return PYZ_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int pyz_stem_destroy(pyz_stem *s) {
   if (!s) return PYZ_OK;
   for (int o = 0; o < s->n_ops; ++o) {
@@ -4124,15 +4160,7 @@ int pyz_convnet_forward(pyz_stem *s, pyz_mlp *m, const float *d_theta, int P, co
                         int batch, float *d_out, void *stream) {
   int rc = convnet_check(s, m, P, batch);
   if (rc) return rc;
-  if (!d_theta || !d_x || !d_out) return pyz_fail(PYZ_E_INVALID, "null device pointer");
-  hipStream_t st = as_stream(stream);
-  if ((rc = set_ctl(m, 0, batch, 0.0f, 0, 0, 0, st))) return rc;
-  convnet_forward(s, m, d_theta, P, d_x, d_row_idx, batch, st);
-  const int C = m->dims[m->L];
-  PYZ_LAUNCH(k_forward_finish, dim3(cdiv(batch, 256), P), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C,
-             m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0, batch, d_out);
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  return net_forward(Net{s, m}, d_theta, P, d_x, d_row_idx, batch, d_out, stream);
 }
 
 int pyz_convnet_loss_grad(pyz_stem *s, pyz_mlp *m, const float *d_theta, int P, const float *d_x, const void *d_y,
@@ -4194,36 +4222,8 @@ int pyz_convnet_predict(pyz_stem *s, pyz_mlp *m, const float *d_weights, int n_s
   int rc = convnet_check(s, m, 1, n);
   if (rc) return rc;
   if (!d_weights || !d_x || !d_mean) return pyz_fail(PYZ_E_INVALID, "null device pointer");
-  hipStream_t st = as_stream(stream);
-  if ((rc = set_ctl(m, 0, n, 0.0f, 0, 0, 0, st))) return rc;
-  const long long Dt = s->D + m->D;
-  const int C = m->dims[m->L];
-  const int softmax = m->acts[m->L - 1] == PYZ_ACT_SOFTMAX ? 1 : 0;
-  PredictMomentsArgs g{};
-  g.last = m->act[m->L - 1];
-  g.C = C;
-  g.pstride = (long long)m->max_batch * C;
-  g.softmax = softmax;
-  g.n = n;
-  g.mean = d_mean;
-  g.m2 = d_m2;
-  g.inv_total = 1.0f / (float)n_samples;
-  for (int s0 = 0; s0 < n_samples; s0 += m->max_p) {
-    const int S = std::min(m->max_p, n_samples - s0);
-    convnet_forward(s, m, d_weights + (long long)s0 * Dt, S, d_x, nullptr, n, st);
-    if (d_m2) {   // the moments form (pyz_predict_moments)
-      g.S = S;
-      g.accumulate = s0 > 0 ? 1 : 0;
-      if (!pyz_launch_predict_moments(g, st)) return pyz_fail(PYZ_E_SHAPE, "a row of %d outputs does not fit the moments kernel's LDS", C);
-      continue;
-    }
-    PYZ_LAUNCH(k_predict_rows, dim3(cdiv(n, 256), S), dim3(256), 0, st, m->act[m->L - 1], (long long)m->max_batch * C, C, softmax, n,
-               d_samples ? d_samples + (long long)s0 * n * C : nullptr);
-    PYZ_LAUNCH(k_predict_mean, dim3((unsigned)cdiv((long long)n * C, 256)), dim3(256), 0, st, m->act[m->L - 1],
-               (long long)m->max_batch * C, (long long)n * C, S, d_mean, s0 > 0 ? 1 : 0, 1.0f / (float)n_samples);
-  }
-  PYZ_LAUNCH_CHECK();
-  return PYZ_OK;
+  if (d_m2) return net_predict_moments(Net{s, m}, d_weights, n_samples, d_x, n, d_mean, d_m2, stream);   // (d_samples unused)
+  return net_predict(Net{s, m}, d_weights, n_samples, d_x, n, d_samples, d_mean, stream);
 }
 
 }  // extern "C"

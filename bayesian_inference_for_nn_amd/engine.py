@@ -67,8 +67,120 @@ def _f32(t: torch.Tensor, shape=None, name="tensor"):
     return t
 
 
-class MLPPlan:
+class _NetPlan:
+    """What a Dense plan and a conv plan share: the argument checks and output allocations of forward, loss_grad, the SGD
+    and SWAG steps and the read-outs.  A class supplies n_in (the width of a row of x), _handles (what its library
+    functions take first), _FN (their names) and _lib_predict."""
+
+    def _net(self, name, *args):
+        check(getattr(self.lib, self._FN[name])(*self._handles, *args, _stream()))
+
+    def _check_xy(self, x, y, row_idx, batch):
+        _f32(x, name="x")
+        if x.dim() != 2 or x.shape[1] != self.n_in:
+            raise ValueError(f"x must be (rows, {self.n_in})")
+        n_rows = x.shape[0]
+        if row_idx is not None:
+            if row_idx.dtype != torch.int32 or not row_idx.is_cuda or not row_idx.is_contiguous():
+                raise TypeError("row_idx must be a contiguous CUDA int32 tensor")
+            if row_idx.numel() < batch:
+                raise ValueError("row_idx holds fewer entries than the batch")
+        elif batch > n_rows:
+            raise ValueError("batch exceeds the rows of x")
+        if y is not None:
+            if self.spec.loss == "scce":
+                if y.dtype != torch.int32 or not y.is_cuda or y.numel() != n_rows:
+                    raise TypeError("labels must be CUDA int32, one per row of x")
+            else:
+                _f32(y, name="y")
+                if y.numel() != n_rows * self.spec.dims[-1]:
+                    raise ValueError("targets must be (rows, out)")
+        if not (1 <= batch <= self.max_batch):
+            raise ValueError(f"batch {batch} outside [1, {self.max_batch}]")
+
+    def _particles(self, theta):
+        P = 1 if theta.dim() == 1 else int(theta.shape[0])
+        _f32(theta, name="theta")
+        if theta.numel() != P * self.D or not 1 <= P <= self.max_particles:
+            raise ValueError(f"theta must be ({self.D},) or (P <= {self.max_particles}, {self.D})")
+        return P
+
+    @staticmethod
+    def _batch(batch, x, row_idx):
+        return int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+
+    # ------------------------------------------------------------------ G1-G3
+    def forward(self, theta, x, batch=None, row_idx=None):
+        P = self._particles(theta)
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, None, row_idx, batch)
+        out = torch.empty((P, batch, self.spec.dims[-1]), dtype=torch.float32, device=self.device)
+        self._net("forward", ptr(theta), P, ptr(x), ptr(row_idx), batch, ptr(out))
+        return out
+
+    def loss_grad(self, theta, x, y, batch=None, row_idx=None, want_grad=True, grad_out=None):
+        P = self._particles(theta)
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, y, row_idx, batch)
+        grad = None
+        if want_grad:
+            grad = grad_out if grad_out is not None else torch.empty((P, self.D), dtype=torch.float32, device=self.device)
+            _f32(grad, (P, self.D), "grad_out")
+        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        self._net("loss_grad", ptr(theta), P, ptr(x), ptr(y), ptr(row_idx), batch, ptr(grad), ptr(loss))
+        return loss, grad
+
+    # ------------------------------------------------------------------ S1
+    def sgd_step(self, theta, x, y, lr, loss_out, batch=None, row_idx=None):
+        _f32(theta, (self.D,), "theta")
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, y, row_idx, batch)
+        self._net("sgd_step", ptr(theta), ptr(x), ptr(y), ptr(row_idx), batch, float(lr), ptr(loss_out))
+
+    def swag_step(self, theta, mean, sq_mean, dev_row, x, y, lr, n, update_moments, loss_out, batch=None, row_idx=None):
+        for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
+            _f32(t, (self.D,), nm)
+        if dev_row is not None:
+            _f32(dev_row, (self.D,), "dev_row")
+        batch = self._batch(batch, x, row_idx)
+        self._check_xy(x, y, row_idx, batch)
+        self._net("swag_step", ptr(theta), ptr(mean), ptr(sq_mean), ptr(dev_row), ptr(x), ptr(y), ptr(row_idx), batch,
+                  float(lr), int(n), 1 if update_moments else 0, ptr(loss_out))
+
+    # ------------------------------------------------------------------ R1
+    def _check_read_out(self, weights, x):
+        _f32(weights, name="weights")
+        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
+            raise ValueError(f"weights must be (draws >= 1, {self.D})")
+        self._check_xy(x, None, None, int(x.shape[0]) if x.dim() == 2 else 0)
+        return int(weights.shape[0]), int(x.shape[0]), self.spec.dims[-1]
+
+    def predict(self, weights, x, want_samples=True):
+        """(samples (S, n, out) or None, mean (n, out)) of the draws `weights` (S, D) on the rows of x."""
+        S, n, C_out = self._check_read_out(weights, x)
+        samples = torch.empty((S, n, C_out), dtype=torch.float32, device=self.device) if want_samples else None
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
+        self._lib_predict(ptr(weights), S, ptr(x), n, ptr(samples), ptr(mean), None)
+        return samples, mean
+
+    def predict_moments(self, weights, x):
+        """(mean (n, out), m2 (n, out, out)) of the draws `weights` (S, D) on the rows of x: mean is predict's mean bit for
+        bit, m2[j] = sum over the draws of p p^T with p = predict's sample of row j.  One kernel per chunk of
+        max_particles draws (pyz_predict_moments); the (S, n, out) sample tensor is never formed."""
+        S, n, C_out = self._check_read_out(weights, x)
+        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
+        m2 = torch.empty((n, C_out, C_out), dtype=torch.float32, device=self.device)
+        self._lib_predict(ptr(weights), S, ptr(x), n, None, ptr(mean), ptr(m2))
+        return mean, m2
+
+
+class MLPPlan(_NetPlan):
     """Owns one `pyz_mlp` handle (device workspace for up to max_batch rows x max_particles)."""
+
+    _FN = {"forward": "pyz_mlp_forward", "loss_grad": "pyz_mlp_loss_grad", "sgd_step": "pyz_sgd_step",
+           "swag_step": "pyz_swag_step"}
+    n_in = property(lambda self: self.spec.dims[0])
+    _handles = property(lambda self: (self.h,))
 
     def __init__(self, spec: MLPSpec, max_batch: int, max_particles: int = 1, device=None):
         if spec.loss == "bce" and (spec.dims[-1] != 1 or spec.acts[-1] != "sigmoid"):
@@ -100,63 +212,7 @@ class MLPPlan:
         except Exception:
             pass
 
-    # ------------------------------------------------------------------ helpers
-    def _check_xy(self, x, y, row_idx, batch):
-        _f32(x, name="x")
-        if x.dim() != 2 or x.shape[1] != self.spec.dims[0]:
-            raise ValueError(f"x must be (rows, {self.spec.dims[0]})")
-        n_rows = x.shape[0]
-        if row_idx is not None:
-            if row_idx.dtype != torch.int32 or not row_idx.is_cuda or not row_idx.is_contiguous():
-                raise TypeError("row_idx must be a contiguous CUDA int32 tensor")
-        elif batch > n_rows:
-            raise ValueError("batch exceeds the rows of x")
-        if y is not None:
-            if self.spec.loss == "scce":
-                if y.dtype != torch.int32 or not y.is_cuda or y.numel() != n_rows:
-                    raise TypeError("labels must be CUDA int32, one per row of x")
-            else:
-                _f32(y, name="y")
-                if y.numel() != n_rows * self.spec.dims[-1]:
-                    raise ValueError("targets must be (rows, out)")
-        if not (1 <= batch <= self.max_batch):
-            raise ValueError(f"batch {batch} outside [1, {self.max_batch}]")
-
-    # ------------------------------------------------------------------ G1-G3
-    def forward(self, theta, x, batch=None, row_idx=None):
-        P = 1 if theta.dim() == 1 else theta.shape[0]
-        _f32(theta, name="theta")
-        assert theta.numel() == P * self.D
-        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
-        self._check_xy(x, None, row_idx, batch)
-        if row_idx is not None:
-            assert row_idx.numel() >= batch
-        out = torch.empty((P, batch, self.spec.dims[-1]), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_mlp_forward(self.h, ptr(theta), P, ptr(x), ptr(row_idx), batch, ptr(out), _stream()))
-        return out
-
-    def loss_grad(self, theta, x, y, batch=None, row_idx=None, want_grad=True):
-        P = 1 if theta.dim() == 1 else theta.shape[0]
-        _f32(theta, name="theta")
-        assert theta.numel() == P * self.D
-        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
-        self._check_xy(x, y, row_idx, batch)
-        if row_idx is not None:
-            assert row_idx.numel() >= batch
-        grad = torch.empty((P, self.D), dtype=torch.float32, device=self.device) if want_grad else None
-        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_mlp_loss_grad(self.h, ptr(theta), P, ptr(x), ptr(y), ptr(row_idx), batch, ptr(grad),
-                                         ptr(loss), _stream()))
-        return loss, grad
-
     # ------------------------------------------------------------------ S1
-    def sgd_step(self, theta, x, y, lr, loss_out, batch=None, row_idx=None):
-        _f32(theta, (self.D,), "theta")
-        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
-        self._check_xy(x, y, row_idx, batch)
-        check(self.lib.pyz_sgd_step(self.h, ptr(theta), ptr(x), ptr(y), ptr(row_idx), batch, float(lr), ptr(loss_out),
-                                    _stream()))
-
     def adam_step(self, theta, m, v, x, y, lr, beta_1, beta_2, epoch, loss_out, denom_eps=1e-3, decay=0.0, batch=None,
                   row_idx=None):
         """ADAM.step (ADAM.py:42-84); VADAM's update with decay = denom_eps = lam / N.  m / v are the moment vectors;
@@ -194,17 +250,6 @@ class MLPPlan:
         check(self.lib.pyz_bsam_step(self.h, ptr(theta), ptr(m), ptr(v), ptr(x), ptr(y), ptr(row_idx), batch, float(lr),
                                      float(beta_1), float(beta_2), float(lam), float(rho), float(gam), float(num_data),
                                      int(step), int(seed), ptr(eps), ptr(loss_out), _stream()))
-
-    def swag_step(self, theta, mean, sq_mean, dev_row, x, y, lr, n, update_moments, loss_out, batch=None, row_idx=None):
-        for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
-            _f32(t, (self.D,), nm)
-        if dev_row is not None:
-            _f32(dev_row, (self.D,), "dev_row")
-        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
-        self._check_xy(x, y, row_idx, batch)
-        check(self.lib.pyz_swag_step(self.h, ptr(theta), ptr(mean), ptr(sq_mean), ptr(dev_row), ptr(x), ptr(y),
-                                     ptr(row_idx), batch, float(lr), int(n), 1 if update_moments else 0, ptr(loss_out),
-                                     _stream()))
 
     # ------------------------------------------------------------------ L2/L3
     def sgld_step(self, theta, mean, sq_mean, x, y, lr, n, seed, loss_out, batch=None, row_idx=None, unit_noise=None):
@@ -764,35 +809,11 @@ class MLPPlan:
         return int(self.lib.pyz_mlp_workspace_bytes(self.h))
 
     # ------------------------------------------------------------------ R1
-    def predict(self, weights, x, want_samples=True):
-        _f32(weights, name="weights")
-        S = weights.shape[0]
-        assert weights.dim() == 2 and weights.shape[1] == self.D
-        _f32(x, name="x")
-        n = x.shape[0]
-        assert x.shape[1] == self.spec.dims[0] and n <= self.max_batch
-        C_out = self.spec.dims[-1]
-        samples = torch.empty((S, n, C_out), dtype=torch.float32, device=self.device) if want_samples else None
-        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_predict(self.h, ptr(weights), S, ptr(x), n, ptr(samples), ptr(mean), _stream()))
-        return samples, mean
-
-    def predict_moments(self, weights, x):
-        """(mean (n, out), m2 (n, out, out)) of the draws `weights` (S, D) on the rows of x: mean is predict's mean bit for
-        bit, m2[j] = sum over the draws of p p^T with p = predict's sample of row j.  One kernel per chunk of
-        max_particles draws (pyz_predict_moments); the (S, n, out) sample tensor is never formed."""
-        _f32(weights, name="weights")
-        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
-            raise ValueError(f"weights must be (draws >= 1, {self.D})")
-        _f32(x, name="x")
-        if x.dim() != 2 or x.shape[1] != self.spec.dims[0]:
-            raise ValueError(f"x must be (rows, {self.spec.dims[0]})")
-        n, C_out = int(x.shape[0]), self.spec.dims[-1]
-        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
-        m2 = torch.empty((n, C_out, C_out), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_predict_moments(self.h, ptr(weights), int(weights.shape[0]), ptr(x), n, ptr(mean), ptr(m2),
-                                           _stream()))
-        return mean, m2
+    def _lib_predict(self, weights, S, x, n, samples, mean, m2):
+        if m2 is None:
+            check(self.lib.pyz_predict(self.h, weights, S, x, n, samples, mean, _stream()))
+        else:
+            check(self.lib.pyz_predict_moments(self.h, weights, S, x, n, mean, m2, _stream()))
 
     def predict_surface(self, weights, x, column=0, want_cols=True, want_summary=True):
         """(cols, mean, top, cls, ent) of the draws `weights` (S, D) on the rows of x, for decision-surface plots:
@@ -800,15 +821,7 @@ class MLPPlan:
         bit for bit, and of each mean row q (one output: the pair (1 - m, m)) top (n,) = max q, cls (n,) int32 = its
         first index, ent (n,) = -sum q log(q + 1e-5), raw (all None without want_summary).  One kernel per chunk of
         max_particles draws (pyz_predict_surface); the (S, n, out) sample tensor is never formed."""
-        _f32(weights, name="weights")
-        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
-            raise ValueError(f"weights must be (draws >= 1, {self.D})")
-        _f32(x, name="x")
-        if x.dim() != 2 or x.shape[1] != self.spec.dims[0] or x.shape[0] < 1:
-            raise ValueError(f"x must be (rows >= 1, {self.spec.dims[0]})")
-        S, n, C_out = int(weights.shape[0]), int(x.shape[0]), self.spec.dims[-1]
-        if n > self.max_batch:
-            raise ValueError(f"{n} rows exceed the plan's max_batch {self.max_batch}")
+        S, n, C_out = self._check_read_out(weights, x)
         column = int(column)
         if not 0 <= column < C_out:
             raise ValueError(f"column {column} outside [0, {C_out})")
@@ -912,10 +925,15 @@ class ConvSpec:
         return [((kh, kw, ci, co), (co,)) for kh, kw, ci, co in self.conv_shapes()] + self.tail.variable_shapes()
 
 
-class ConvPlan:
+class ConvPlan(_NetPlan):
     """Owns one `pyz_stem` handle and the MLPPlan of the Dense tail: the forward, gradient, SGD / SWAG step and read-out
     of a conv net (pyz_convnet_*), with MLPPlan's argument conventions.  x: (rows, H * W * C) float32, images row-major
     (h, w, c)."""
+
+    _FN = {"forward": "pyz_convnet_forward", "loss_grad": "pyz_convnet_loss_grad", "sgd_step": "pyz_convnet_sgd_step",
+           "swag_step": "pyz_convnet_swag_step"}
+    n_in = property(lambda self: int(np.prod(self.spec.input_shape)))
+    _handles = property(lambda self: (self.h, self.tail.h))
 
     def __init__(self, spec: ConvSpec, max_batch: int, max_particles: int = 1, device=None):
         self.lib = _lib.load()
@@ -965,47 +983,12 @@ class ConvPlan:
         except Exception:
             pass
 
-    def workspace_bytes(self):
-        return int(self.lib.pyz_stem_workspace_bytes(self.h)) + int(self.lib.pyz_mlp_workspace_bytes(self.tail.h))
+    @property
+    def workspace_bytes(self) -> int:
+        return int(self.lib.pyz_stem_workspace_bytes(self.h)) + self.tail.workspace_bytes
 
     def check_finite(self):
         self.tail.check_finite()
-
-    # ------------------------------------------------------------------ helpers
-    def _check_xy(self, x, y, row_idx, batch):
-        _f32(x, name="x")
-        n_in = int(np.prod(self.spec.input_shape))
-        if x.dim() != 2 or x.shape[1] != n_in:
-            raise ValueError(f"x must be (rows, {n_in})")
-        n_rows = x.shape[0]
-        if row_idx is not None:
-            if row_idx.dtype != torch.int32 or not row_idx.is_cuda or not row_idx.is_contiguous():
-                raise TypeError("row_idx must be a contiguous CUDA int32 tensor")
-            if row_idx.numel() < batch:
-                raise ValueError("row_idx holds fewer entries than the batch")
-        elif batch > n_rows:
-            raise ValueError("batch exceeds the rows of x")
-        if y is not None:
-            if self.spec.loss == "scce":
-                if y.dtype != torch.int32 or not y.is_cuda or y.numel() != n_rows:
-                    raise TypeError("labels must be CUDA int32, one per row of x")
-            else:
-                _f32(y, name="y")
-                if y.numel() != n_rows * self.spec.dims[-1]:
-                    raise ValueError("targets must be (rows, out)")
-        if not (1 <= batch <= self.max_batch):
-            raise ValueError(f"batch {batch} outside [1, {self.max_batch}]")
-
-    def _particles(self, theta):
-        P = 1 if theta.dim() == 1 else int(theta.shape[0])
-        _f32(theta, name="theta")
-        if theta.numel() != P * self.D or not 1 <= P <= self.max_particles:
-            raise ValueError(f"theta must be ({self.D},) or (P <= {self.max_particles}, {self.D})")
-        return P
-
-    @staticmethod
-    def _batch(batch, x, row_idx):
-        return int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
 
     # ------------------------------------------------------------------ the stem alone
     def stem_forward(self, theta, x, batch=None, row_idx=None, out=None):
@@ -1031,69 +1014,9 @@ class ConvPlan:
                                          ptr(grad), self.D_stem, _stream()))
         return grad
 
-    # ------------------------------------------------------------------ the whole net (MLPPlan's methods)
-    def forward(self, theta, x, batch=None, row_idx=None):
-        P = self._particles(theta)
-        batch = self._batch(batch, x, row_idx)
-        self._check_xy(x, None, row_idx, batch)
-        out = torch.empty((P, batch, self.spec.dims[-1]), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_convnet_forward(self.h, self.tail.h, ptr(theta), P, ptr(x), ptr(row_idx), batch, ptr(out),
-                                           _stream()))
-        return out
-
-    def loss_grad(self, theta, x, y, batch=None, row_idx=None, want_grad=True, grad_out=None):
-        P = self._particles(theta)
-        batch = self._batch(batch, x, row_idx)
-        self._check_xy(x, y, row_idx, batch)
-        grad = None
-        if want_grad:
-            grad = grad_out if grad_out is not None else torch.empty((P, self.D), dtype=torch.float32, device=self.device)
-            _f32(grad, (P, self.D), "grad_out")
-        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_convnet_loss_grad(self.h, self.tail.h, ptr(theta), P, ptr(x), ptr(y), ptr(row_idx), batch,
-                                             ptr(grad), ptr(loss), _stream()))
-        return loss, grad
-
-    def sgd_step(self, theta, x, y, lr, loss_out, batch=None, row_idx=None):
-        _f32(theta, (self.D,), "theta")
-        batch = self._batch(batch, x, row_idx)
-        self._check_xy(x, y, row_idx, batch)
-        check(self.lib.pyz_convnet_sgd_step(self.h, self.tail.h, ptr(theta), ptr(x), ptr(y), ptr(row_idx), batch, float(lr),
-                                            ptr(loss_out), _stream()))
-
-    def swag_step(self, theta, mean, sq_mean, dev_row, x, y, lr, n, update_moments, loss_out, batch=None, row_idx=None):
-        for t, nm in ((theta, "theta"), (mean, "mean"), (sq_mean, "sq_mean")):
-            _f32(t, (self.D,), nm)
-        if dev_row is not None:
-            _f32(dev_row, (self.D,), "dev_row")
-        batch = self._batch(batch, x, row_idx)
-        self._check_xy(x, y, row_idx, batch)
-        check(self.lib.pyz_convnet_swag_step(self.h, self.tail.h, ptr(theta), ptr(mean), ptr(sq_mean), ptr(dev_row), ptr(x),
-                                             ptr(y), ptr(row_idx), batch, float(lr), int(n), 1 if update_moments else 0,
-                                             ptr(loss_out), _stream()))
-
-    def _check_read_out(self, weights, x):
-        _f32(weights, name="weights")
-        if weights.dim() != 2 or weights.shape[1] != self.D or weights.shape[0] < 1:
-            raise ValueError(f"weights must be (draws >= 1, {self.D})")
-        self._check_xy(x, None, None, int(x.shape[0]) if x.dim() == 2 else 0)
-        return int(weights.shape[0]), int(x.shape[0]), self.spec.dims[-1]
-
-    def predict(self, weights, x, want_samples=True):
-        S, n, C_out = self._check_read_out(weights, x)
-        samples = torch.empty((S, n, C_out), dtype=torch.float32, device=self.device) if want_samples else None
-        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_convnet_predict(self.h, self.tail.h, ptr(weights), S, ptr(x), n, ptr(samples), ptr(mean), None,
-                                           _stream()))
-        return samples, mean
-
-    def predict_moments(self, weights, x):
-        S, n, C_out = self._check_read_out(weights, x)
-        mean = torch.empty((n, C_out), dtype=torch.float32, device=self.device)
-        m2 = torch.empty((n, C_out, C_out), dtype=torch.float32, device=self.device)
-        check(self.lib.pyz_convnet_predict(self.h, self.tail.h, ptr(weights), S, ptr(x), n, None, ptr(mean), ptr(m2),
-                                           _stream()))
-        return mean, m2
+    # ------------------------------------------------------------------ the whole net: _NetPlan's methods
+    def _lib_predict(self, weights, S, x, n, samples, mean, m2):
+        check(self.lib.pyz_convnet_predict(self.h, self.tail.h, weights, S, x, n, samples, mean, m2, _stream()))
 
 
 def make_plan(spec, max_batch: int, max_particles: int = 1, device=None):

@@ -14,6 +14,11 @@ import numpy as np
 from .model import Array, DenseNet, model_from_json
 
 
+def _host(a) -> np.ndarray:
+    """a (NumPy, array-like, or something with ``.numpy()``) as a NumPy array."""
+    return np.asarray(a.numpy() if hasattr(a, "numpy") else a)
+
+
 class BayesianModel:
     def __init__(self, model_config: str):
         self._model_config = model_config
@@ -117,8 +122,10 @@ class BayesianModel:
     # ------------------------------------------------------------------ read-out
     _predict_rows_cap = 16384      # rows per launch sequence of predict (more rows: several sequences, results joined on the device)
 
-    def _read_out_plan(self, n: int, nb_samples: int) -> int:
-        """Rows per launch sequence of a read-out of n rows and nb_samples draws; self._plan serves them afterwards.
+    def _read_out_plan(self, n: int, nb_samples: int, spec=None):
+        """(rows per launch sequence, the plan that serves them) of a read-out of n rows and nb_samples draws: the plan of
+        the model's own spec, kept in self._plan, or (adversarial_examples) of the given loss-carrying spec, kept in
+        self._grad_plan.
         Bounds the activation workspace: rows x samples per launch (the plan keeps an activation and a delta buffer per
         layer: 2 * sum(widths) floats per (sample, row)).  2^29 floats = 2 GiB of the 288: 100 draws x 10 000 rows of the
         784 -> 200 -> 10 model go out as ONE launch per layer (3.35 ms for the wide layer against 7 x 0.61 ms in seven)."""
@@ -126,9 +133,42 @@ class BayesianModel:
         rows = min(n, int(self._predict_rows_cap))
         per = 2 * sum(int(d) for d in self._model.dims[1:]) + self._stem_floats()
         chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
-        if self._plan is None or self._plan.max_batch < rows or self._plan.max_particles < chunk_s:
-            self._plan = make_plan(self._model.spec, max_batch=rows, max_particles=chunk_s)
-        return rows
+        attr, spec = ("_plan", self._model.spec) if spec is None else ("_grad_plan", spec)
+        plan = getattr(self, attr)
+        if plan is None or plan.spec != spec or plan.max_batch < rows or plan.max_particles < chunk_s:
+            plan = make_plan(spec, max_batch=rows, max_particles=chunk_s)
+            setattr(self, attr, plan)
+        return rows, plan
+
+    @staticmethod
+    def _device_rows(x):
+        """Rows given as NumPy, as something with ``.numpy()`` or as a CUDA tensor (rows made on the device stay there),
+        as the (n, -1) contiguous float32 device tensor."""
+        import torch
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.to(torch.float32).reshape(len(x), -1).contiguous()
+        x = _host(x)
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))).cuda()   # (no host copy of float32 input)
+
+    @staticmethod
+    def _walk_rows(n: int, rows: int, chunk, row_axis=()):
+        """``chunk(r0, count)`` -> a tuple of device tensors (None where an output is not wanted) for every chunk of at
+        most `rows` of the n rows; returns the tuple for all n rows.  A single chunk's tensors are returned as they are, no
+        copy; otherwise the full outputs are allocated once and each chunk's are written into their slices.  row_axis[k]:
+        the axis of output k that runs over the rows (0 where not given)."""
+        full = None
+        for r0 in range(0, n, rows):
+            part = chunk(r0, min(rows, n - r0))
+            if rows >= n:
+                return part
+            axes = tuple(row_axis) + (0,) * (len(part) - len(row_axis))
+            if full is None:
+                full = tuple(None if t is None else t.new_empty(t.shape[:a] + (n,) + t.shape[a + 1:])
+                             for t, a in zip(part, axes))
+            for out, t, a in zip(full, part, axes):
+                if t is not None:
+                    out.narrow(a, r0, t.shape[a]).copy_(t)
+        return full
 
     def _is_conv(self) -> bool:
         return hasattr(self._model.spec, "ops")
@@ -149,25 +189,12 @@ class BayesianModel:
     def predict(self, x, nb_samples: int, y_true=None, loss_func=None):
         """(list of per-sample outputs, their mean); NaN outputs count as 0 (BayesianModel.py:106-129)."""
         import torch
-        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))   # (no copy of float32 input)
+        xd = self._device_rows(x)
         nb_samples = int(nb_samples)
         Wd = self.sample_weights_device(nb_samples)
-        n = len(x)
-        rows = self._read_out_plan(n, nb_samples)
-        xd = torch.as_tensor(x).cuda()
-        C_out = int(self._model.dims[-1])
-        full = mean_full = None
-        for r0 in range(0, n, rows):
-            samples_d, mean_d = self._plan.predict(Wd, xd[r0:r0 + rows].contiguous())
-            if rows >= n:
-                full, mean_full = samples_d, mean_d
-            else:
-                if full is None:
-                    full = torch.empty((nb_samples, n, C_out), dtype=torch.float32, device=xd.device)
-                    mean_full = torch.empty((n, C_out), dtype=torch.float32, device=xd.device)
-                full[:, r0:r0 + rows] = samples_d
-                mean_full[r0:r0 + rows] = mean_d
+        rows, plan = self._read_out_plan(len(xd), nb_samples)
+        full, mean_full = self._walk_rows(len(xd), rows, lambda r0, cnt: plan.predict(Wd, xd[r0:r0 + cnt].contiguous()),
+                                          row_axis=(1,))
         # one device-to-host copy of each result into pinned memory (the 40 MB sample tensor of 100 draws x 10 000 rows
         # moves at PCIe rate instead of through the driver's pageable staging); the NumPy views keep the buffers alive
         samples_h = torch.empty(full.shape, dtype=torch.float32, pin_memory=True)
@@ -183,35 +210,17 @@ class BayesianModel:
     def _read_out(self, x, nb_samples: int, moments: bool):
         """predict's draws, row cap and workspace rule; per row chunk MLPPlan.predict_moments (moments) or the mean-only
         MLPPlan.predict: device (mean (n, C), m2 (n, C, C) or None).  No sample tensor is formed."""
-        import torch
-        if isinstance(x, torch.Tensor) and x.is_cuda:       # rows made on the device (corruption_scores) stay there
-            xd = x.to(torch.float32).reshape(len(x), -1).contiguous()
-        else:
-            x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
-            x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
-            xd = None
+        xd = self._device_rows(x)       # (rows made on the device, as corruption_scores', stay there)
         nb_samples = int(nb_samples)
         Wd = self.sample_weights_device(nb_samples)
-        n = len(x)
-        rows = self._read_out_plan(n, nb_samples)
-        if xd is None:
-            xd = torch.as_tensor(x).cuda()
-        C_out = int(self._model.dims[-1])
-        mean_full = m2_full = None
-        for r0 in range(0, n, rows):
-            xc = xd[r0:r0 + rows].contiguous()
-            mean_d, m2_d = self._plan.predict_moments(Wd, xc) if moments else (self._plan.predict(Wd, xc, want_samples=False)[1], None)
-            if rows >= n:
-                mean_full, m2_full = mean_d, m2_d
-            else:
-                if mean_full is None:
-                    mean_full = torch.empty((n, C_out), dtype=torch.float32, device=xd.device)
-                    m2_full = torch.empty((n, C_out, C_out), dtype=torch.float32, device=xd.device) if moments else None
-                mean_full[r0:r0 + rows] = mean_d
-                if moments:
-                    m2_full[r0:r0 + rows] = m2_d
+        rows, plan = self._read_out_plan(len(xd), nb_samples)
+
+        def chunk(r0, cnt):
+            xc = xd[r0:r0 + cnt].contiguous()
+            return plan.predict_moments(Wd, xc) if moments else (plan.predict(Wd, xc, want_samples=False)[1], None)
+        mean, m2 = self._walk_rows(len(xd), rows, chunk)
         self._model.set_flat(Wd[-1].cpu().numpy())      # the reference leaves the last draw assigned
-        return mean_full, m2_full
+        return mean, m2
 
     def predictive_moments(self, x, nb_samples: int):
         """(mean (n, C), m2 (n, C, C), nb_samples) as NumPy float32 arrays: the Monte-Carlo mean of ``predict`` (bit for
@@ -229,7 +238,6 @@ class BayesianModel:
         """The read-out behind predictive_surface / grid_surface: predict's draws, row cap and workspace rule; per row
         chunk ``rows_of(r0, count)`` hands the device rows and MLPPlan.predict_surface reads them out.  NumPy
         (cols (S, n) or None, mean (n, C), top (n,), cls (n,) int32, ent (n,))."""
-        import torch
         nb_samples, n = int(nb_samples), int(n)
         if n < 1 or nb_samples < 1:
             raise ValueError("rows and nb_samples must be positive")
@@ -237,21 +245,11 @@ class BayesianModel:
         if not 0 <= int(column) < C_out:
             raise ValueError(f"column {column} outside [0, {C_out})")
         Wd = self.sample_weights_device(nb_samples)
-        rows = self._read_out_plan(n, nb_samples)
-        dev = Wd.device
-        cols = torch.empty((nb_samples, n), dtype=torch.float32, device=dev) if want_cols else None
-        mean = torch.empty((n, C_out), dtype=torch.float32, device=dev)
-        top = torch.empty((n,), dtype=torch.float32, device=dev)
-        cls = torch.empty((n,), dtype=torch.int32, device=dev)
-        ent = torch.empty((n,), dtype=torch.float32, device=dev)
-        for r0 in range(0, n, rows):
-            c, m, t, k, e = self._plan.predict_surface(Wd, rows_of(r0, min(rows, n - r0)), column=column, want_cols=want_cols)
-            if want_cols:
-                cols[:, r0:r0 + rows] = c
-            mean[r0:r0 + rows], top[r0:r0 + rows], cls[r0:r0 + rows], ent[r0:r0 + rows] = m, t, k, e
+        rows, plan = self._read_out_plan(n, nb_samples)
+        out = self._walk_rows(n, rows, lambda r0, cnt: plan.predict_surface(Wd, rows_of(r0, cnt), column=column,
+                                                                            want_cols=want_cols), row_axis=(1,))
         self._model.set_flat(Wd[-1].cpu().numpy())      # the reference leaves the last draw assigned
-        return (cols.cpu().numpy() if want_cols else None, mean.cpu().numpy(), top.cpu().numpy(), cls.cpu().numpy(),
-                ent.cpu().numpy())
+        return tuple(None if t is None else t.cpu().numpy() for t in out)
 
     def predictive_surface(self, x, nb_samples: int, column: int = 0, want_cols: bool = False):
         """(cols, mean, top, cls, ent) as NumPy arrays for the rows of x: mean (n, C) = ``predict``'s mean (bit for bit,
@@ -259,10 +257,8 @@ class BayesianModel:
         ent = -sum q log(q + 1e-5) in float32, raw; cols (nb_samples, n) = column `column` of every draw's prediction, or
         None.  Computed on the device by pyz_predict_surface: the sample tensor is neither written nor copied."""
         self._refuse_conv("predictive_surface")
-        import torch
-        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
-        xd = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))).cuda()
-        return self._surface(len(x), nb_samples, column, want_cols, lambda r0, cnt: xd[r0:r0 + cnt].contiguous())
+        xd = self._device_rows(x)
+        return self._surface(len(xd), nb_samples, column, want_cols, lambda r0, cnt: xd[r0:r0 + cnt].contiguous())
 
     def grid_surface(self, basis, a0, da, n1, b0, db, n2, nb_samples: int, column: int = 0, want_cols: bool = False):
         """``predictive_surface`` on the n1 x n2 grid u_i = a0 + i da, v_j = b0 + j db ('ij' row order), each grid point
@@ -295,15 +291,13 @@ class BayesianModel:
         image and no mean leaves the device."""
         import torch
         from .. import engine
-        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
+        x, y = _host(x), _host(y)
         n = len(x)
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(n, -1))
-        y = np.asarray(y.numpy() if hasattr(y, "numpy") else y)
         if n < 1 or len(y) != n:
             raise ValueError("x and y must hold the same, positive number of rows")
+        xd = self._device_rows(x)
         sev = [int(s) for s in severities]
         C_out = int(self._model.dims[-1])
-        xd = torch.as_tensor(x).cuda()
         if regression:
             yd = torch.as_tensor(np.ascontiguousarray(y.astype(np.float32).reshape(n, -1))).cuda()
             if yd.shape[1] != C_out:
@@ -329,7 +323,7 @@ class BayesianModel:
         labels or targets in [0, 1], one per row)."""
         self._refuse_conv("adversarial_examples")
         import torch
-        from ..engine import MLPPlan, MLPSpec
+        from ..engine import MLPSpec
         if loss not in ("scce", "mse", "bce"):
             raise ValueError(f"loss must be 'scce', 'mse' or 'bce', not {loss!r}")
         spec = MLPSpec(tuple(self._model.spec.dims), tuple(self._model.spec.acts), loss)
@@ -337,11 +331,8 @@ class BayesianModel:
                 (loss == "bce" and (spec.dims[-1] != 1 or spec.acts[-1] != "sigmoid")):
             raise ValueError("'scce' needs a softmax last layer, 'mse' a last layer that is not softmax, "
                              "'bce' a last layer of one sigmoid unit")
-        x = np.asarray(x.numpy() if hasattr(x, "numpy") else x)
-        shape = x.shape
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1))
-        n = len(x)
-        y = np.asarray(y.numpy() if hasattr(y, "numpy") else y)
+        x, y = _host(x), _host(y)
+        shape, n = x.shape, len(x)
         if loss == "scce":
             y = np.ascontiguousarray(y.reshape(-1).astype(np.int32))
         else:
@@ -350,21 +341,14 @@ class BayesianModel:
             raise ValueError("x and y must hold the same, positive number of rows")
         nb_samples = int(nb_samples)
         Wd = self.sample_weights_device(nb_samples)
-        rows = min(n, int(self._predict_rows_cap))       # the workspace rule of predict
-        per = 2 * sum(int(d) for d in self._model.dims[1:])
-        chunk_s = max(1, min(nb_samples, int(os.environ.get("PYZ_PREDICT_WS", 1 << 29)) // max(1, rows * per)))
-        plan = self._grad_plan
-        if plan is None or plan.spec != spec or plan.max_batch < rows or plan.max_particles < chunk_s:
-            plan = self._grad_plan = MLPPlan(spec, max_batch=rows, max_particles=chunk_s)
-        xd, yd = torch.as_tensor(x).cuda(), torch.as_tensor(y).cuda()
-        grad = torch.empty_like(xd)
-        adv = torch.empty_like(xd)
-        for r0 in range(0, n, rows):
-            xc, yc = xd[r0:r0 + rows].contiguous(), yd[r0:r0 + rows].contiguous()
+        rows, plan = self._read_out_plan(n, nb_samples, spec)       # the workspace rule of predict
+        xd, yd = self._device_rows(x), torch.as_tensor(y).cuda()
+
+        def chunk(r0, cnt):
             # a chunk's mean loss is over its own rows: chunk_rows / n of it is its share of the mean over all n
-            g, a, _ = plan.input_grad(Wd, xc, yc, scale=len(xc) / n, epsilon=float(epsilon))
-            grad[r0:r0 + rows] = g
-            adv[r0:r0 + rows] = a
+            return plan.input_grad(Wd, xd[r0:r0 + cnt].contiguous(), yd[r0:r0 + cnt].contiguous(), scale=cnt / n,
+                                   epsilon=float(epsilon))[:2]
+        grad, adv = self._walk_rows(n, rows, chunk)
         plan.check_finite()
         return adv.cpu().numpy().reshape(shape), grad.cpu().numpy().reshape(shape)
 

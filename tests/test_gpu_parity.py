@@ -211,6 +211,35 @@ def test_shape_errors_are_reported_not_faulted(eng):
         p2.loss_grad(dev(theta), dev(x[:8]), ydev(spec, y[:8]))  # SCCE without softmax
 
 
+def test_bad_input_of_a_dense_plan_is_a_value_error_as_of_a_conv_plan(eng):
+    """What a kernel cannot check is refused before a pointer leaves Python, by exceptions that `python -O` keeps (no
+    assert): the messages are the ones a ConvPlan gives."""
+    spec, _ = SPECS["tiny_cls"]
+    x, y, theta = make(spec, 12)
+    plan = eng.MLPPlan(espec(eng, spec), max_batch=8, max_particles=2)
+    th, xd, yd = dev(theta), dev(x[:8]), ydev(spec, y[:8])
+    W = dev(np.stack([theta, theta, theta]))
+    idx = dev(np.arange(4), torch.int32)
+    for call in (lambda: plan.forward(th[:-1].contiguous(), xd), lambda: plan.loss_grad(th[:-1].contiguous(), xd, yd),
+                 lambda: plan.forward(W, xd)):                                    # three particles for a plan of two
+        with pytest.raises(ValueError, match="theta must be"):
+            call()
+    with pytest.raises(ValueError, match="weights must be"):
+        plan.predict(W[:, :-1].contiguous(), xd)
+    for call in (lambda: plan.forward(th, xd[:, :-1].contiguous()), lambda: plan.loss_grad(th, xd[:, :-1].contiguous(), yd),
+                 lambda: plan.predict(W, xd[:, :-1].contiguous())):
+        with pytest.raises(ValueError, match=r"x must be \(rows, 5\)"):
+            call()
+    for call in (lambda: plan.forward(th, dev(x)), lambda: plan.predict(W, dev(x))):     # 12 rows > max_batch 8
+        with pytest.raises(ValueError, match=r"batch 12 outside \[1, 8\]"):
+            call()
+    for call in (lambda: plan.forward(th, xd, batch=6, row_idx=idx), lambda: plan.loss_grad(th, xd, yd, batch=6, row_idx=idx)):
+        with pytest.raises(ValueError, match="row_idx holds fewer entries than the batch"):
+            call()
+    assert plan.forward(th, xd, row_idx=idx).shape == (1, 4, 3) and plan.predict(W, xd)[0].shape == (3, 8, 3)
+    plan.close()
+
+
 # ------------------------------------------------------------------ SGD
 def test_sgd_steps_match_oracle(eng):
     spec = o_mlp.MLPSpec((1, 1), ("linear",), "mse")

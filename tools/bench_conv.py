@@ -127,7 +127,7 @@ def main():
            "swag_step_us": round(float(np.median(ours)), 1), "swag_step_us_rounds": [round(v, 1) for v in ours],
            "kernels": split, "kernel_us_total": round(sum(t for _, t in kp.launches), 1), "conv": conv,
            "torch_eager_step_us": round(float(np.median(theirs)), 1), "torch_eager_step_us_rounds": [round(v, 1) for v in theirs],
-           "workspace_mb": round(plan.workspace_bytes() / 1e6, 1)}
+           "workspace_mb": round(plan.workspace_bytes / 1e6, 1)}
     res["ratio_torch_over_ours"] = round(res["torch_eager_step_us"] / res["swag_step_us"], 2)
     print(json.dumps(res))
 
