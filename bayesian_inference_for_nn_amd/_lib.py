@@ -71,6 +71,7 @@ SIGNATURES = {
                                        C.POINTER(_f), C.c_int, _i64, _i64, _p, C.c_int, _p]),
     "pyz_last_run_info": (C.c_int, [_p, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "pyz_sgld_run_info": (C.c_int, [_p, C.POINTER(_i32)]),
+    "pyz_run_batch_form": (C.c_int, [_p, C.POINTER(_i32)]),
     "pyz_check_finite": (C.c_int, [_p, _p]),
     "pyz_probe_begin": (C.c_int, [C.c_int]),
     "pyz_probe_end": (C.c_int, [_p, C.POINTER(_f), C.c_char_p, C.c_int, C.POINTER(C.c_int)]),

@@ -237,9 +237,9 @@ DenseArgs forward_args(pyz_mlp *m, int l, const float *theta, long long theta_ps
 void launch_forward(pyz_mlp *m, const float *theta, long long theta_ps, int P, const float *x,
                     const int32_t *row_idx, int grid_batch, const StepCtl *ctl, hipStream_t st,
                     float *gather_out = nullptr, int l_end = -1, const StepCtl *gate = nullptr, int gate_mod = 0,
-                    long long x_pstride = 0) {
+                    long long x_pstride = 0, int l_begin = 0) {
   if (l_end < 0) l_end = m->L;
-  for (int l = 0; l < l_end; ++l) {
+  for (int l = l_begin; l < l_end; ++l) {
     DenseArgs g = forward_args(m, l, theta, theta_ps, x, row_idx, ctl, gather_out);
     if (l == 0) g.in_pstride = x_pstride;   // (a conv net's Dense tail: one set of rows, the stem's features, per particle)
     g.wt = pyz_wt_for(P);
@@ -509,6 +509,25 @@ void launch_wgrad_all(pyz_mlp *m, int P, const float *x, const int32_t *row_idx,
   }
 }
 
+// launch_wgrad_all of a run that keeps its batches as images (one chain, an updating mode): layer 0 reads this step's
+// weight-gradient image wimg, and the workers leave the next batch as images too (a.prep.dst is a slot of images).  The same
+// tiles, waves and grid.
+void launch_wgrad_all_frag(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl, WgradArgs &a,
+                           hipStream_t st, const float *wimg) {
+  const int tiles = wgrad_layers(m, 1, x, row_idx, ctl, a, wimg);
+  const int S = pyz_pick_waves(tiles, (grid_batch + 1) / 2);
+  dim3 grid((unsigned)tiles + 1);  // + the duties workgroup
+  if (a.prep.src) grid.x = (unsigned)(tiles + 1 + std::max(pyz_cu_count() - tiles - 1, 24));  // + the batch workers
+  a.lay[0].lda = 8 * ((m->max_batch + 7) / 8);   // rows of the image
+  switch (S) {
+    case 1: PYZ_LAUNCH_AS(k_wgrad_all<1>, k_wgrad_all_frag<1>, grid, dim3(64), 0, st, a); break;
+    case 2: PYZ_LAUNCH_AS(k_wgrad_all<2>, k_wgrad_all_frag<2>, grid, dim3(128), 2 * 4096, st, a); break;
+    case 4: PYZ_LAUNCH_AS(k_wgrad_all<4>, k_wgrad_all_frag<4>, grid, dim3(256), 4 * 4096, st, a); break;
+    case 8: PYZ_LAUNCH_AS(k_wgrad_all<8>, k_wgrad_all_frag<8>, grid, dim3(512), 8 * 4096, st, a); break;
+    default: PYZ_LAUNCH_AS(k_wgrad_all<16>, k_wgrad_all_frag<16>, grid, dim3(1024), 16 * 4096, st, a); break;
+  }
+}
+
 // ADAM / VADAM (one chain): every layer's gradient and squared-gradient mean, and the update, in one launch
 void launch_wgrad_adam(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, const StepCtl *ctl, AdamArgs &a,
                        hipStream_t st, const float *gathered) {
@@ -556,6 +575,27 @@ inline bool batch_ahead(const pyz_mlp *m, const int32_t *row_idx) {
   return on == 2 || wgrad_tiles(m) + 24 <= pyz_cu_count();
 }
 
+// The image form of the batches assembled ahead (PrepArgs, pyz_fused.h): a slot is the forward image and the weight-gradient
+// image behind it.  PYZ_BATCH_FRAG [1] is read when the plan is created (the images are larger than the two row-major copies).
+inline size_t frag_fwd_floats(const pyz_mlp *m) { return (size_t)((m->max_batch + 31) / 32) * 32 * m->dims[0]; }
+inline size_t frag_slot_floats(const pyz_mlp *m) {
+  return frag_fwd_floats(m) + (size_t)((m->dims[0] + 31) / 32) * ((m->max_batch + 7) / 8) * 256;
+}
+inline float *frag_buf(pyz_mlp *m, int slot) { return m->xb + (size_t)slot * frag_slot_floats(m); }
+
+// Does this run keep its batches as images?  Only where layer 0's forward is k_dense_fwd and the weight gradients are
+// k_wgrad_all with `theta` the weights it multiplies: the SGD / SGLD / SWAG / BBB runs of sgld_run_impl, one chain.
+bool batch_frag(pyz_mlp *m, const float *theta, const float *x, const int32_t *row_idx, int grid_batch) {
+  if (!m->frag_on || !batch_ahead(m, row_idx)) return false;
+  const int K = m->dims[0];
+  if (K % 8 || !aligned16(x) || !aligned16(m->xb)) return false;
+  if (pyz_env_int("PYZ_FWD_KSPLIT", 0) >= 2) return false;   // (the split-reduction forward reads rows)
+  DenseArgs g = forward_args(m, 0, theta, m->D, frag_buf(m, 0), nullptr, nullptr, nullptr);
+  if (!g.vec || pyz_fwd_ring_variant(g, grid_batch, 1)) return false;
+  const long long tiles = (long long)((grid_batch + 31) / 32) * ((g.N + 31) / 32);
+  return !pyz_fwd_takes_lds(g, grid_batch, 1, pyz_pick_waves(tiles, (g.K + 1) / 2 + 1));
+}
+
 PrepArgs prep_args(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_batch, long long row_stride, int dst_slot) {
   PrepArgs p{};
   p.src = x;
@@ -566,6 +606,12 @@ PrepArgs prep_args(pyz_mlp *m, const float *x, const int32_t *row_idx, int grid_
   p.K = p.lda = m->dims[0];
   p.fwd_tiles_n = (m->dims[1] + 31) / 32;
   p.fwd_tiles = ((grid_batch + 31) / 32) * p.fwd_tiles_n;
+  return p;
+}
+
+// prep_args of a run that keeps its batches as images: the destination is a slot of images
+inline PrepArgs frag_prep(pyz_mlp *m, PrepArgs p, int dst_slot) {
+  p.dst = frag_buf(m, dst_slot);
   return p;
 }
 
@@ -594,8 +640,19 @@ int ksplit_for(pyz_mlp *m, const float *theta, long long theta_ps, int P, const 
 // squared-gradient kernels write their means to grad2 beside upd.grad (unfused path)
 void launch_loss_backward(pyz_mlp *m, const float *theta, long long theta_ps, int P, const float *x, const void *y,
                           const int32_t *row_idx, int grid_batch, const StepCtl *ctl, bool want_grad, WgradArgs &upd,
-                          hipStream_t st, int ahead_slot = -1, AdamArgs *adam = nullptr) {
+                          hipStream_t st, int ahead_slot = -1, AdamArgs *adam = nullptr, bool frag = false) {
   if (can_fuse(m)) {
+    if (ahead_slot >= 0 && frag) {   // this step's rows stand as images in frag_buf(ahead_slot) (batch_frag)
+      DenseArgs g = forward_args(m, 0, theta, theta_ps, frag_buf(m, ahead_slot), nullptr, ctl, nullptr);
+      g.wt = pyz_wt_for(P);
+      g.rows_cap = std::min(grid_batch, m->max_batch);
+      pyz_launch_fwd_frag(g, grid_batch, st);
+      launch_forward(m, theta, theta_ps, P, nullptr, nullptr, grid_batch, ctl, st, nullptr, m->L - 1, nullptr, 0, 0, 1);
+      launch_head(m, theta, theta_ps, P, x, y, row_idx, grid_batch, ctl, want_grad, st);   // (labels go through row_idx)
+      launch_bwd_data_hidden(m, theta, theta_ps, P, grid_batch, ctl, st);
+      launch_wgrad_all_frag(m, x, row_idx, grid_batch, ctl, upd, st, frag_buf(m, ahead_slot) + frag_fwd_floats(m));
+      return;
+    }
     if (ahead_slot >= 0) {
       const float *xc = batch_buf(m, ahead_slot);
       // one hidden layer of <= 200 units, one chain: the forward with its reduction split over PYZ_FWD_KSPLIT workgroups per
@@ -1046,7 +1103,10 @@ int pyz_mlp_create(int n_layers, const int32_t *h_dims, const int32_t *h_acts, i
   }
   {
     // two contiguous batches: chained runs assemble step s + 1's rows in the one that step s does not read
-    const size_t bytes = 2 * sizeof(float) * (size_t)max_batch * m->dims[0] + 64;
+    // (or, PYZ_BATCH_FRAG [1] and an input width the images exist for, two slots of images: frag_slot_floats)
+    m->frag_on = pyz_env_int("PYZ_BATCH_FRAG", 1) != 0 && m->dims[0] % 8 == 0;
+    size_t bytes = 2 * sizeof(float) * (size_t)max_batch * m->dims[0] + 64;
+    if (m->frag_on) bytes = std::max(bytes, 2 * sizeof(float) * frag_slot_floats(m) + 64);
     if (hipMalloc((void **)&m->xb, bytes) != hipSuccess) return fail(pyz_fail(PYZ_E_OOM, "workspace allocation of %zu bytes failed", bytes));
     m->ws_bytes += bytes;
   }
@@ -1575,6 +1635,9 @@ struct RunBc {
 static int upload_run_tables(pyz_mlp *m, const int32_t *h_batch_sizes, const float *h_lr, int n_steps, int64_t n0, int64_t slot0,
                              const RunBc *bc, const float *d_x, const int32_t *d_row_idx, int ahead_batch, hipStream_t st) {
   Extra &x = full(m)->x;
+  const bool frag = m->frag_next && ahead_batch;   // (set by sgld_run_impl for the call it is about to make; every other run: rows)
+  m->frag_next = false;
+  m->run_batch_form = ahead_batch ? (frag ? 2 : 1) : 0;
   int rc;
   const size_t n_tab = (size_t)n_steps + 1;
   if ((rc = ensure_run_tables(m, n_tab, bc ? 16 : 8, st))) return rc;
@@ -1601,7 +1664,8 @@ static int upload_run_tables(pyz_mlp *m, const int32_t *h_batch_sizes, const flo
     for (int s = 0; bc && s <= n_steps; ++s) ibc.bc[s] = bc->of(std::min(s, n_steps - 1));
     if (ahead_batch) {   // ... together with the first batch of the run
       const PrepArgs pa = prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0);
-      if (bc) PYZ_LAUNCH(k_run_start_bc, dim3(256), dim3(256), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, x.tab_bc, (long long)n0, slot0 * row_stride, (int)slot0, pa);
+      if (frag) PYZ_LAUNCH_AS(k_run_start, k_run_start_frag, dim3(256), dim3(256), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0, frag_prep(m, pa, 0));
+      else if (bc) PYZ_LAUNCH(k_run_start_bc, dim3(256), dim3(256), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, x.tab_bc, (long long)n0, slot0 * row_stride, (int)slot0, pa);
       else PYZ_LAUNCH(k_run_start, dim3(256), dim3(256), 0, st, m->ctl, tabs, m->tab_bs, m->tab_lr, (long long)n0, slot0 * row_stride, (int)slot0, pa);
     } else {
       if (bc) PYZ_LAUNCH(k_set_ctl_tabs_bc, dim3(1), dim3(64), 0, st, m->ctl, tabs, ibc, m->tab_bs, m->tab_lr, x.tab_bc, (long long)n0, slot0 * row_stride, (int)slot0);
@@ -1625,6 +1689,10 @@ static int upload_run_tables(pyz_mlp *m, const int32_t *h_batch_sizes, const flo
   if (bc) PYZ_HIP(hipMemcpyAsync(x.tab_bc, hc, sizeof(float2) * n_tab, hipMemcpyHostToDevice, st));
   PYZ_HIP(hipEventRecord(x.tab_ev[slot], st));
   if ((rc = set_ctl(m, 0, h_batch_sizes[0], h_lr[0], n0, slot0 * row_stride, 0, st, (int)slot0, n_steps))) return rc;
+  if (frag) {   // the first batch of the run as images
+    PYZ_LAUNCH_AS(k_prep_batch, k_prep_batch_frag, dim3(256), dim3(256), 0, st, frag_prep(m, prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0), 0), m->ctl);
+    return PYZ_OK;
+  }
   if (ahead_batch)   // the first batch of the run (every later one is assembled by the step before it)
     PYZ_LAUNCH(k_prep_batch, dim3(256), dim3(256), 0, st, prep_args(m, d_x, d_row_idx, ahead_batch, row_stride, 0), m->ctl);
   return PYZ_OK;
@@ -1635,6 +1703,7 @@ static void launch_sgld_step(pyz_mlp *m, float *theta, float *mean, float *sq, c
                              uint64_t seed, const float *unit_noise, float *loss, hipStream_t st, int mode = PYZ_UPD_SGLD,
                              const SwagChain *swag = nullptr, const BbbChain *bbb = nullptr, bool first = true) {
   const StepCtl *ctl = m->ctl + slot;
+  const bool frag = chained && m->run_batch_form == 2;   // the run keeps its batches as images (upload_run_tables)
   if (bbb) {   // BBB.step (BBB.py:128-211) inside a device-resident run: scalars from StepCtl, cost into slot (slot0 + i)
     // Sampling fused (bbb->w2): the weights and the log q - log p partials of step i + 1 come out of step i's weight-gradient
     // epilogue, into the buffers of the other StepCtl slot; only the first step of a chunk launches k_bbb_sample (for a later
@@ -1689,7 +1758,8 @@ static void launch_sgld_step(pyz_mlp *m, float *theta, float *mean, float *sq, c
     u.row_stride = row_stride;
     const bool ahead = chained && batch_ahead(m, row_idx);
     if (ahead) u.prep = prep_args(m, x, row_idx, grid_batch, row_stride, slot ^ 1);
-    launch_loss_backward(m, w_cur, m->D, 1, x, y, row_idx, grid_batch, ctl, true, u, st, ahead ? slot : -1);
+    if (ahead && frag) u.prep.dst = frag_buf(m, slot ^ 1);
+    launch_loss_backward(m, w_cur, m->D, 1, x, y, row_idx, grid_batch, ctl, true, u, st, ahead ? slot : -1, nullptr, ahead && frag);
     if (bbb->val) {   // the validation split through the weights this step sampled; the launches do nothing on every tenth step
       pyz_mlp *v = bbb->val;
       launch_forward(v, w_cur, v->D, 1, bbb->val_x, nullptr, bbb->n_val, v->ctl, st, nullptr, v->L - 1, ctl, 10);
@@ -1720,7 +1790,8 @@ static void launch_sgld_step(pyz_mlp *m, float *theta, float *mean, float *sq, c
     u.row_stride = row_stride;
     const bool ahead = chained && batch_ahead(m, row_idx);
     if (ahead) u.prep = prep_args(m, x, row_idx, grid_batch, row_stride, slot ^ 1);
-    launch_loss_backward(m, theta, m->D, 1, x, y, row_idx, grid_batch, ctl, true, u, st, ahead ? slot : -1);
+    if (ahead && frag) u.prep.dst = frag_buf(m, slot ^ 1);
+    launch_loss_backward(m, theta, m->D, 1, x, y, row_idx, grid_batch, ctl, true, u, st, ahead ? slot : -1, nullptr, ahead && frag);
     return;
   }
   WgradArgs u{};
@@ -1801,6 +1872,8 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
   }
   const long long row_stride = m->max_batch;
   // every step is launched for the largest batch of the call: the first batch is placed for its forward tiles too
+  // ... and, where the step's kernels are the ones that read them, as images (the same answer for every step of the call)
+  const bool frag = m->frag_next = batch_frag(m, d_theta, d_x, d_row_idx, bmax);
   if ((rc = upload_run_tables(m, h_batch_sizes, h_lr, n_steps, n0, slot0, nullptr, d_x, d_row_idx,
                               batch_ahead(m, d_row_idx) ? bmax : 0, st)))
     return rc;
@@ -1823,6 +1896,7 @@ static int sgld_run_impl(pyz_mlp *m, float *d_theta, float *d_mean, float *d_sq_
     mix((unsigned long long)(uintptr_t)d_y); mix((unsigned long long)(uintptr_t)d_row_idx);
     mix((unsigned long long)(uintptr_t)d_losses); mix(seed); mix((unsigned long long)bmax);
     mix((unsigned long long)(uintptr_t)m->tab_bs); mix((unsigned long long)G); mix((unsigned long long)mode);
+    mix(frag ? 1ull : 0ull);
     // (not the stream: an instantiated graph launches on any stream, and a caller that takes a fresh stream per run --
     // torch hands them out of a pool -- would otherwise re-capture every graph on every call)
     if (swag) { mix((unsigned long long)(uintptr_t)swag->dev); mix((unsigned long long)swag->k); mix((unsigned long long)swag->freq); }
@@ -3922,6 +3996,12 @@ int pyz_last_run_info(const pyz_mlp *m, int32_t *h_graph_steps, int32_t *h_eager
   if (h_graph_steps) *h_graph_steps = m->run_graph_steps;
   if (h_eager_steps) *h_eager_steps = m->run_eager_steps;
   if (h_graph_launches) *h_graph_launches = m->run_graph_launches;
+  return PYZ_OK;
+}
+
+int pyz_run_batch_form(const pyz_mlp *m, int32_t *h_form) {
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (h_form) *h_form = m->run_batch_form;
   return PYZ_OK;
 }
 

@@ -203,6 +203,21 @@ inline PyzProbe &pyz_probe() {
     }                                                                                                            \
   } while (0)
 
+// PYZ_LAUNCH of a kernel that stands in for another one in some runs (the image forms of the step kernels, pyz_fused.h): the
+// probe files it under `as`, the kernel whose launch it replaces, so that everything keyed by the probe's names -- bench.py's
+// roofline picks k_dense_fwd / k_head_rows / k_wgrad_all by name, the launch tables of the run tests -- reads the step as
+// before.  Which form a run used is pyz_run_batch_form's answer; a profiler's trace shows the kernel's own name.
+#define PYZ_LAUNCH_AS(as, kern, grid, block, lds, st, ...)                                                       \
+  do {                                                                                                           \
+    PyzProbe &pp_ = pyz_probe();                                                                                 \
+    if (pp_.on && pp_.n < pp_.cap) {                                                                             \
+      hipExtLaunchKernelGGL(kern, grid, block, lds, st, pp_.ev[2 * pp_.n], pp_.ev[2 * pp_.n + 1], 0, __VA_ARGS__); \
+      pp_.name[pp_.n++] = #as;                                                                                   \
+    } else {                                                                                                     \
+      hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                                               \
+    }                                                                                                            \
+  } while (0)
+
 // ---------------------------------------------------------------- captured graphs of the device-resident runs
 // N slots, each a graph of `len` steps captured for `sig` (whatever else tells two graphs of one length apart).  Everything
 // baked into ALL of them is hashed into `key` by the caller: rekey() drops every graph when it changes.
@@ -289,6 +304,9 @@ struct pyz_mlp {
   float *act[PYZ_MAX_LAYERS] = {nullptr};    // output of layer l: (P, max_batch, dims[l+1])
   float *delta[PYZ_MAX_LAYERS] = {nullptr};  // d loss / d pre-activation of layer l, same shape
   float *xb = nullptr;                       // (max_batch, dims[0]) contiguous copy of the gathered batch rows
+  bool frag_on = false;                      // xb is large enough for two slots of batch images (PYZ_BATCH_FRAG, dims[0] % 8 == 0)
+  int run_batch_form = 0;                    // the last run's batches: 0 gathered by each step, 1 assembled ahead as rows, 2 as images
+  bool frag_next = false;                    // sgld_run_impl -> upload_run_tables: the run about to start keeps its batches as images
   float *grad = nullptr;                     // (P, D)
   float *grad2 = nullptr;                    // (P, D) second scratch (HMC momentum, SVGD phi)
   float *qsave = nullptr;                    // (P, D) HMC snapshot

@@ -584,6 +584,75 @@ struct PrepArgs {
   int fwd_tiles, fwd_tiles_n; // tile grid of the forward kernel that will read dst (pyz_xcd_remap over fwd_tiles ids)
 };
 
+// The image form of the next batch (pyz_prep_rows<true>; SGD / SGLD / SWAG / BBB runs with K % 8 == 0): instead of the
+// row-major copy the workers leave the batch twice, each time in the order the MFMA fragments of its reader want it, in
+// 1 KiB blocks of 64 pieces of 16 bytes -- piece l is what lane l of the reading wave loads, so one wave-instruction
+// covers eight whole 128-byte lines.  With mb = row_stride (the plan's max_batch), RB = ceil(mb / 32), C8 = K / 8,
+// KB = ceil(K / 32), G = ceil(mb / 8):
+//   forward image, at dst, RB x C8 blocks: block (rb, c), piece r + 32 h = X[32 rb + r][8 c + 4 h .. + 3]
+//       float offset (((rb C8 + c) 2 + h) 32 + r) 4 + q                     (k_dense_fwd_frag)
+//   weight-gradient image, at dst + 32 RB K, KB x G blocks: block (kb, g), piece i + 32 h = column 32 kb + i of rows
+//       8 g + h + {0, 2, 4, 6}: that lane's A values of the MFMA steps 4 g .. 4 g + 3
+//       float offset (((kb G + g) 2 + h) 32 + i) 4 + q                      (k_wgrad_all_frag, layer 0)
+// Columns at or past K of the last column block are zeros; rows at or past the batch hold nothing defined (both readers
+// select them away).
+__device__ __forceinline__ long long pyz_frag_fwd_floats(const int mb, const int K) { return (long long)((mb + 31) >> 5) * 32 * K; }
+
+// the row groups of eight that begin in rows [ra, rb) of the batch of nb rows, as both images (the workers' shares are
+// consecutive ranges of [0, nb): every group has one owner).  A wave takes one row group of one column block at a time, eight rows x 32 columns: lane (r8, c) loads the 16 bytes of columns 4 c .. 4 c + 3 of row 8 g + r8 -- whole
+// 128-byte lines of eight source rows -- and stores them as they are, a piece of the forward image: the eight lanes of a c
+// fill one line.  The four lanes (h + 2 q, c), q = 0 .. 3, then transpose their 4 x 4 values among themselves (four lane
+// permutes), which leaves each of them one piece of the weight-gradient image, and the wave stores that block's whole KiB
+// in one instruction.  No store leaves part of a line to a later one (they are write-through), and the loads of four such
+// units are in flight before the first store.
+__device__ __forceinline__ void pyz_copy_rows_frag(const PrepArgs &g, const int32_t *idx, const int ra, const int rb, const int nb) {
+  const int ga = (ra + 7) >> 3, gb = (rb + 7) >> 3;
+  if (ga >= gb) return;
+  const int K = g.K, K4 = K >> 2, C8 = K >> 3, KB = (K + 31) >> 5;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int r8 = lane & 7, cl = lane >> 3, h = r8 & 1, qd = r8 >> 1;
+  const int mb = (int)g.row_stride, G = (mb + 7) >> 3;
+  float *fimg = g.dst, *wimg = g.dst + pyz_frag_fwd_floats(mb, K);
+  const int total = (gb - ga) * KB;                       // units: (row group, column block)
+  for (int u0 = wv; u0 < total; u0 += 4 * nw) {           // (uniform per wave)
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int unit = min(u0 + u * nw, total - 1), gi = ga + unit / KB, c4 = 8 * (unit % KB) + cl;
+      const int m = min(8 * gi + r8, nb - 1);             // (rows past the batch, columns past K: any defined element)
+      v[u] = *reinterpret_cast<const float4 *>(g.src + (long long)idx[m] * g.lda + 4 * min(c4, K4 - 1));
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int unit = u0 + u * nw;
+      if (unit >= total) break;
+      const int gi = ga + unit / KB, kb = unit % KB, c4 = 8 * kb + cl, m = 8 * gi + r8;
+      const bool vc = c4 < K4;
+      if (vc && m < nb) {
+        float *d = fimg + ((((long long)(m >> 5) * C8 + (c4 >> 1)) * 2 + (c4 & 1)) * 32 + (m & 31)) * 4;
+        const f32x4 vv = {v[u].x, v[u].y, v[u].z, v[u].w};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(d), "v"(vv) : "memory");   // (write-through: see pyz_copy_rows)
+      }
+      // round k: lane q sends its column (q + k) % 4; lane qd takes from lane (qd - k) % 4 that lane's column qd, its row's value
+      const float x0 = vc ? v[u].x : 0.0f, x1 = vc ? v[u].y : 0.0f, x2 = vc ? v[u].z : 0.0f, x3 = vc ? v[u].w : 0.0f;
+      float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int js = (qd + k) & 3, qs = (qd - k) & 3;
+        const float send = js == 0 ? x0 : (js == 1 ? x1 : (js == 2 ? x2 : x3));
+        const float got = __shfl(send, (cl << 3) | (2 * qs + h), 64);
+        o0 = qs == 0 ? got : o0;
+        o1 = qs == 1 ? got : o1;
+        o2 = qs == 2 ? got : o2;
+        o3 = qs == 3 ? got : o3;
+      }
+      float *dw = wimg + ((((long long)kb * G + gi) * 2 + h) * 32 + 4 * cl + qd) * 4;
+      const f32x4 ww = {o0, o1, o2, o3};
+      asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dw), "v"(ww) : "memory");
+    }
+  }
+}
+
 // rows [ra, rb) of the batch whose row indices start at idx: dst[m][:] = src[idx[m]][:]
 __device__ __forceinline__ void pyz_copy_rows(const PrepArgs &g, const int32_t *idx, const int ra, const int rb) {
   const int K = g.K, nt = blockDim.x, t = threadIdx.x;
@@ -619,7 +688,9 @@ __device__ __forceinline__ void pyz_copy_rows(const PrepArgs &g, const int32_t *
   }
 }
 
-// worker j of cnt (its workgroup id is bid): its share of the nb rows
+// worker j of cnt (its workgroup id is bid): its share of the nb rows.  FRAG: as the two images (the row groups that begin
+// in the share)
+template <bool FRAG = false>
 __device__ __forceinline__ void pyz_prep_rows(const PrepArgs &g, const int32_t *idx, const int nb, const int j, const int cnt,
                                               const int bid) {
   int ra, rb;
@@ -642,12 +713,16 @@ __device__ __forceinline__ void pyz_prep_rows(const PrepArgs &g, const int32_t *
     ra = j * per;
     rb = min(ra + per, nb);
   }
-  pyz_copy_rows(g, idx, ra, rb);
+  if (FRAG) pyz_copy_rows_frag(g, idx, ra, rb, nb);
+  else pyz_copy_rows(g, idx, ra, rb);
 }
 
 // the first batch of a run (nobody ran before it): the same copy as a launch of its own
 __global__ void k_prep_batch(PrepArgs g, const StepCtl *ctl) {
   pyz_prep_rows(g, g.row_idx + ctl->row_off, ctl->batch, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+}
+__global__ void k_prep_batch_frag(PrepArgs g, const StepCtl *ctl) {   // ... as the two images
+  pyz_prep_rows<true>(g, g.row_idx + ctl->row_off, ctl->batch, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
 }
 
 // short runs (the tables travel as kernel arguments): k_set_ctl_tabs and k_prep_batch as ONE launch in front of the
@@ -672,6 +747,28 @@ __global__ void k_run_start(StepCtl *ctl, InlineTabs t, int32_t *tab_bs, float *
     }
   }
   pyz_prep_rows(g, g.row_idx + row_off, t.bs[0], (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+}
+
+// k_run_start of a run that keeps its batches as images (a kernel of its own: k_run_start stays what it was)
+__global__ void k_run_start_frag(StepCtl *ctl, InlineTabs t, int32_t *tab_bs, float *tab_lr, long long n, long long row_off,
+                                 int slot0, PrepArgs g) {
+  if (blockIdx.x == 0) {
+    const int e = threadIdx.x;
+    if (e < t.n) {
+      tab_bs[e] = t.bs[e];
+      tab_lr[e] = t.lr[e];
+    }
+    if (e == 0) {
+      ctl->batch = t.bs[0];
+      ctl->lr = t.lr[0];
+      ctl->n = n;
+      ctl->row_off = row_off;
+      ctl->i = 0;
+      ctl->slot0 = slot0;
+      ctl->n_run = t.n - 1;
+    }
+  }
+  pyz_prep_rows<true>(g, g.row_idx + row_off, t.bs[0], (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
 }
 
 // k_run_start with the bias-correction table of a device-resident ADAM / VADAM run (k_set_ctl_tabs_bc)
@@ -914,11 +1011,56 @@ __device__ __forceinline__ void pyz_wgrad_accumulate(f32x16 &acc, const float *a
   }
 }
 
+// pyz_wgrad_accumulate with layer 0's A operand out of the weight-gradient image of the batch (PrepArgs): ablk = this lane's
+// piece of row group 0 in the tile's column block, row group g 256 floats further.  One float4 per lane carries the A values
+// of the steps 4 g .. 4 g + 3, delta stays one dword per step.  The wave's steps [s, se) run in ascending order exactly as
+// above: a group at either end of the range that the wave owns only in part is loaded whole, and the steps outside the range
+// are skipped (uniform), not multiplied by zero.
+template <class H>
+__device__ __forceinline__ void pyz_wgrad_accumulate_frag(f32x16 &acc, const float *ablk, const float *dbase, const int n,
+                                                          const int N, const int batch, const int s, const int se,
+                                                          const int h, const bool is_w, const bool is_b, H hook) {
+  const float bconst = is_b ? 1.0f : 0.0f;
+  const unsigned d_lane = ((unsigned)h * (unsigned)N + (unsigned)n) * 4u;
+  const unsigned d_row2 = 8u * (unsigned)N;  // bytes per MFMA step (two rows)
+  const __amdgpu_buffer_rsrc_t rd =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(dbase), 0, (int)((unsigned)batch * (unsigned)N * 4u), 0x00020000);
+  const int full = batch >> 1, sf = min(se, full);   // only whole steps here; the odd last row is peeled (see above)
+  const int cb = s >> 2, ce = s < sf ? (sf + 3) >> 2 : cb;
+  const int dlast = max(full - 1, 0);                // (the scalar offset is not range checked: no step past the last whole one)
+  pyz_pipe4x<2>(
+      cb, ce,
+      [&](int c, float4 &a4, float4 &d4) {
+        const int cc = PYZ_HOT(c, batch);
+        a4 = *reinterpret_cast<const float4 *>(ablk + 256 * cc);
+        const unsigned s0 = (unsigned)min(4 * cc, dlast), s1 = (unsigned)min(4 * cc + 1, dlast);
+        const unsigned s2 = (unsigned)min(4 * cc + 2, dlast), s3 = (unsigned)min(4 * cc + 3, dlast);
+        d4 = make_float4(pyz_buf_load(rd, d_lane, s0 * d_row2), pyz_buf_load(rd, d_lane, s1 * d_row2),
+                         pyz_buf_load(rd, d_lane, s2 * d_row2), pyz_buf_load(rd, d_lane, s3 * d_row2));
+      },
+      [&](int c, float4 &a4, float4 &d4) {
+        const int st = 4 * c;
+        if (st >= s && st < sf) acc = pyz_mfma(is_w ? a4.x : bconst, d4.x, acc);
+        if (st + 1 >= s && st + 1 < sf) acc = pyz_mfma(is_w ? a4.y : bconst, d4.y, acc);
+        if (st + 2 >= s && st + 2 < sf) acc = pyz_mfma(is_w ? a4.z : bconst, d4.z, acc);
+        if (st + 3 >= s && st + 3 < sf) acc = pyz_mfma(is_w ? a4.w : bconst, d4.w, acc);
+      },
+      hook);
+  if (se > full) {  // this wave owns the odd last row (step `full`, h = 0): the second reduction slot of its MFMA stays empty
+    const int b = batch - 1;
+    float a = ablk[256 * (full >> 2) + (full & 3)], d = dbase[(size_t)b * N + n];
+    a = h == 0 ? (is_w ? a : bconst) : 0.0f;
+    d = h == 0 ? d : 0.0f;
+    acc = pyz_mfma(a, d, acc);
+  }
+}
+
 // One tile of k_wgrad_all, MODE (the optimizer update) a compile-time constant: the kernel branches once on g.mode, so the
 // prefetch hook and the epilogue of an SGLD step hold no other mode's instructions, registers or branches (as one body
 // with a run-time mode, BBB's fused sampling -- softplus, logs, the log q - log p reduction -- and SWAG's gated moments lay
 // between the SGLD instructions).
-template <int S, bool PLAIN, int MODE>
+// FRAG: layer 0's entry describes the weight-gradient image of the batch (in = the image, lda = its rows, 8 G).
+template <int S, bool PLAIN, int MODE, bool FRAG = false>
 __device__ __forceinline__ void pyz_wgrad_tile(const WgradArgs &g, float *red) {
   constexpr int EPT = 16 / S;  // tile elements per thread in the epilogue
   const int w = pyz_wave_id(), l = threadIdx.x & 63;
@@ -1004,7 +1146,13 @@ __device__ __forceinline__ void pyz_wgrad_tile(const WgradArgs &g, float *red) {
   int s = (steps * w) / S;
   const int se = (steps * (w + 1)) / S;
   PYZ_STAMP(2, 1);
-  if (idx) {
+  if (FRAG && li == 0) {   // (uniform)
+    // the tile's column block of the image; a tile that holds only the bias row (K % 32 == 0) reads the last block and
+    // uses none of it
+    const int kb = min(i0, K - 1) >> 5, G = ly.lda >> 3;
+    pyz_wgrad_accumulate_frag(acc, ly.in + ((long long)kb * G * 64 + l) * 4, ly.delta + p * ly.delta_pstride, n, N, batch, s,
+                              se, h, is_w, is_b, prefetch);
+  } else if (idx) {
     prefetch();
     // gathered rows: the 64 row indices of a 32-step chunk come from ONE coalesced load (lane j
     // holds the index of batch row 2*s0 + j) and reach the step that needs them by a lane
@@ -1144,6 +1292,38 @@ __global__ void __launch_bounds__(64 * S) k_wgrad_all(WgradArgs g) {
       case PYZ_UPD_BBB: pyz_wgrad_tile<S, false, PYZ_UPD_BBB>(g, red); break;
       default: pyz_wgrad_tile<S, false, PYZ_UPD_NONE>(g, red); break;
     }
+  }
+}
+
+// k_wgrad_all of a run whose batches stand as images: layer 0's tiles read this step's weight-gradient image
+// (pyz_wgrad_tile<.., true>) and the workers leave the next batch as images.  One chain, an updating mode; a kernel of its own,
+// so that every k_wgrad_all<S> stays what it was.
+template <int S>
+__global__ void __launch_bounds__(64 * S) k_wgrad_all_frag(WgradArgs g) {
+  extern __shared__ float red[];
+  PYZ_STAMP(2, 0);
+  const int w = pyz_wave_id(), l = threadIdx.x & 63;
+  asm volatile("; arguments in one trip" ::"s"(g.tiles), "s"(g.mode), "s"(g.ctl), "s"(g.row_idx), "s"(g.tile0[1]),
+               "s"(g.tile0[2]), "s"(g.tile0[3]), "s"(g.tile0[4]), "s"(g.tile0[5]), "s"(g.tile0[6]), "s"(g.tile0[7]),
+               "s"(g.tile0[8]), "s"(g.tile0[9]), "s"(g.tile0[10]), "s"(g.tile0[11]), "s"(g.tile0[12]), "s"(g.tile0[13]),
+               "s"(g.tile0[14]), "s"(g.tile0[15]));
+  if (blockIdx.x >= (unsigned)g.tiles) {
+    if (blockIdx.x == (unsigned)g.tiles && w == 0) pyz_step_duties(g, l);
+    if (blockIdx.x > (unsigned)g.tiles && g.prep.src) {
+      const int i2 = g.ctl->i + 1;
+      if (i2 < g.ctl->n_run)
+        pyz_prep_rows<true>(g.prep, g.prep.row_idx + g.ctl->row_off + g.prep.row_stride, g.prep.tab_bs[i2],
+                            (int)blockIdx.x - g.tiles - 1, (int)gridDim.x - g.tiles - 1, (int)blockIdx.x);
+      PYZ_STAMP(2, 3);
+    }
+    return;
+  }
+  switch (g.mode) {   // (uniform) one instruction stream per update mode
+    case PYZ_UPD_SGLD: pyz_wgrad_tile<S, false, PYZ_UPD_SGLD, true>(g, red); break;
+    case PYZ_UPD_SGD: pyz_wgrad_tile<S, false, PYZ_UPD_SGD, true>(g, red); break;
+    case PYZ_UPD_SWAG: pyz_wgrad_tile<S, false, PYZ_UPD_SWAG, true>(g, red); break;
+    case PYZ_UPD_BBB: pyz_wgrad_tile<S, false, PYZ_UPD_BBB, true>(g, red); break;
+    default: __builtin_trap();   // no other mode's run assembles images
   }
 }
 

@@ -281,6 +281,41 @@ __device__ __forceinline__ void pyz_pipe4(int c, const int ce, f32x16 &acc, L lo
   }
 }
 
+// pyz_pipe4 with the matrix instructions of a step left to the caller: `body(c, a4, b4)` masks and multiplies
+template <int G, class L, class B, class H = PyzNoHook>
+__device__ __forceinline__ void pyz_pipe4x(int c, const int ce, L load, B body, H hook = H()) {
+  if (c >= ce) {
+    hook();
+    return;
+  }
+  float4 an[G], bn[G], a[G], b[G];
+  const int last = ce - 1;
+#pragma unroll
+  for (int u = 0; u < G; ++u) load(min(c + u, last), an[u], bn[u]);
+  __builtin_amdgcn_sched_barrier(0);
+  hook();   // runs once, behind the first group's loads (see pyz_pipe1)
+  __builtin_amdgcn_sched_barrier(0);
+  for (;;) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      a[u] = an[u];
+      b[u] = bn[u];
+    }
+    const int cn = c + G;
+    if (cn < ce) {
+#pragma unroll
+      for (int u = 0; u < G; ++u) load(min(cn + u, last), an[u], bn[u]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < G; ++u)
+      if (c + u < ce) body(c + u, a[u], b[u]);
+    __builtin_amdgcn_sched_barrier(0);
+    c = cn;
+    if (c >= ce) break;
+  }
+}
+
 template <class L, class U, class H = PyzNoHook>
 __device__ __forceinline__ void pyz_steps4_all(int c, const int ce, f32x16 &acc, L load, U use, H hook = H()) {
   pyz_pipe4<2>(c, ce, acc, load, use, hook);
@@ -302,7 +337,10 @@ __device__ __forceinline__ float pyz_buf_load(const __amdgpu_buffer_rsrc_t rsrc,
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)voff, (int)soff, 0));
 }
 
-template <class H = PyzNoHook>
+// FRAG: ap = this lane's 16-byte piece of chunk 0 in the forward image of the batch (see PrepArgs, pyz_fused.h): chunk c of
+// the row block is the 1 KiB at ap + 256 c, so the 64 lanes of a load cover whole contiguous lines.  The same float4 as
+// ap + 8 c + 4 h of the row-major form; K % 8 == 0 (no tail steps), no copy to store.
+template <bool FRAG = false, class H = PyzNoHook>
 __device__ __forceinline__ void pyz_fwd_accumulate(f32x16 &acc, const float *ap, const float *wl, const int n, const int K,
                                                    const int N, const int vec, const int w, const int S, const int h,
                                                    float *gp = nullptr, const int copy_mod = 1, const int copy_rem = 0,
@@ -321,13 +359,13 @@ __device__ __forceinline__ void pyz_fwd_accumulate(f32x16 &acc, const float *ap,
       0, (c8 - w + S - 1) / S, acc,
       [&](int u, float4 &a4, float4 &b4) {
         const int c = PYZ_HOT(w + S * u, K);
-        a4 = *reinterpret_cast<const float4 *>(ap + 8 * c + 4 * h);
+        a4 = *reinterpret_cast<const float4 *>(FRAG ? ap + 256 * c : ap + 8 * c + 4 * h);
         const unsigned so = 8u * (unsigned)c * N4;
         b4 = make_float4(pyz_buf_load(rw, v0, so), pyz_buf_load(rw, v1, so), pyz_buf_load(rw, v2, so), pyz_buf_load(rw, v3, so));
       },
       [&](int u, const float4 &a4) {
         const int c = w + S * u;
-        if (gp && c % copy_mod == copy_rem) {
+        if (!FRAG && gp && c % copy_mod == copy_rem) {
 #ifdef PYZ_COPY_NT   // diagnostic: streaming stores for the batch copy
           typedef float pyz_f4 __attribute__((ext_vector_type(4)));
           pyz_f4 v = {a4.x, a4.y, a4.z, a4.w};
@@ -338,9 +376,9 @@ __device__ __forceinline__ void pyz_fwd_accumulate(f32x16 &acc, const float *ap,
         }
       },
       hook);
-  const int t0 = 8 * c8, steps = (K - t0 + 1) >> 1;
+  const int t0 = 8 * c8, steps = FRAG ? 0 : (K - t0 + 1) >> 1;
   const unsigned vt = (unsigned)h * N4 + n4;
-  pyz_steps1_all(
+  if (!FRAG) pyz_steps1_all(
       0, (steps - w + S - 1) / S, acc,
       [&](int u, float &a, float &b) {
         const int kb = t0 + 2 * (w + S * u);
@@ -409,6 +447,43 @@ __global__ void k_dense_fwd(DenseArgs g) {
   batch = g.rows_cap > 0 ? __builtin_amdgcn_readfirstlane(batch) : cap;
   PYZ_STAMP(0, 2);
   float *op = g.out + p * g.out_pstride;
+  const int act = g.act, wt = g.wt;
+  pyz_tile_epilogue(acc, red, [&](int ro, int co, float v) {
+    const int mm = m0 + ro, nn = n0 + co;
+    if (mm < batch && nn < N) pyz_st(op + (long long)mm * N + nn, pyz_act(v, act), wt);
+  });
+  PYZ_STAMP(0, 3);
+}
+
+// k_dense_fwd of layer 0 over the forward image of a batch assembled ahead (PrepArgs, pyz_fused.h): g.in is the image,
+// g.rows_cap > 0, one chain, K % 8 == 0; no gather, no gate, no copy.  The same tiles, waves, chunk ownership, MFMAs and
+// epilogue -- a kernel of its own, so that k_dense_fwd stays what it was.
+__global__ void k_dense_fwd_frag(DenseArgs g) {
+  extern __shared__ float red[];
+  PYZ_STAMP(0, 0);
+  const int S = blockDim.x >> 6, w = pyz_wave_id(), l = threadIdx.x & 63;
+  const int r = l & 31, h = l >> 5;
+  const int tiles_n = (g.N + 31) >> 5;
+  asm volatile("; arguments in one trip" ::"s"(g.in), "s"(g.theta), "s"(g.w_off), "s"(g.K), "s"(g.N), "s"(g.vec), "s"(g.rows_cap),
+               "s"(g.out), "s"(g.ctl), "s"(g.act), "s"(g.wt), "s"((int)gridDim.x), "s"((int)blockDim.x));
+  const int tile = pyz_xcd_remap(blockIdx.x, gridDim.x);
+  const int m0 = (tile / tiles_n) * 32, n0 = (tile % tiles_n) * 32;
+  if (m0 >= g.rows_cap) return;  // uniform per workgroup
+  const int K = g.K, N = g.N;
+  const int n = min(n0 + r, N - 1);
+  // row block m0 / 32 is K / 8 blocks of 1 KiB, lane l owns bytes [16 l, 16 l + 16) of each.  Every row of the block stands
+  // in the image, so no row is clamped: rows past the batch are computed and dropped, as in k_dense_fwd
+  const float *ap = g.in + ((long long)(m0 >> 5) * (K >> 3) * 64 + l) * 4;
+  const float *wl = g.theta + g.w_off;
+  f32x16 acc = {0};
+  PYZ_STAMP(0, 1);
+  int batch = 0;   // (the late load of the step's batch: see k_dense_fwd)
+  const int32_t *ctl_batch = &g.ctl->batch;
+  pyz_fwd_accumulate<true>(acc, ap, wl, n, K, N, g.vec, w, S, h, nullptr, 1, 0,
+                           [&]() { batch = __hip_atomic_load(ctl_batch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
+  batch = __builtin_amdgcn_readfirstlane(batch);
+  PYZ_STAMP(0, 2);
+  float *op = g.out;
   const int act = g.act, wt = g.wt;
   pyz_tile_epilogue(acc, red, [&](int ro, int co, float v) {
     const int mm = m0 + ro, nn = n0 + co;
@@ -819,6 +894,14 @@ static inline void pyz_launch_fwd(const DenseArgs &g, int grid_batch, int P, hip
     return;
   }
   PYZ_LAUNCH(k_dense_fwd, dim3(pyz_pad8(tiles, P), P), dim3(64 * S), S > 1 ? S * 4096 : 0, st, g);
+}
+
+// layer 0 over the forward image of a batch assembled ahead (one chain; the caller has checked that pyz_launch_fwd would
+// launch k_dense_fwd): the same grid, the same waves
+static inline void pyz_launch_fwd_frag(const DenseArgs &g, int grid_batch, hipStream_t st) {
+  const long long tiles = (long long)((grid_batch + 31) / 32) * ((g.N + 31) / 32);
+  const int S = pyz_pick_waves(tiles, (g.K + 1) / 2 + 1);
+  PYZ_LAUNCH_AS(k_dense_fwd, k_dense_fwd_frag, dim3((unsigned)tiles), dim3(64 * S), S > 1 ? S * 4096 : 0, st, g);
 }
 
 static inline void pyz_launch_bwd_data(const DenseArgs &g, int grid_batch, int P, hipStream_t st) {

@@ -510,6 +510,14 @@ class MLPPlan(_NetPlan):
         check(self.lib.pyz_sgld_run_info(self.h, C.byref(n)))
         return n.value
 
+    def run_batch_form(self) -> str:
+        """Where the steps of the last device-resident run on this plan found their batch rows: "gather" (each step gathered
+        its own), "rows" (assembled one step ahead as contiguous rows) or "images" (assembled one step ahead in the order the
+        kernels' MFMA fragments read them: PYZ_BATCH_FRAG)."""
+        n = C.c_int32()
+        check(self.lib.pyz_run_batch_form(self.h, C.byref(n)))
+        return ("gather", "rows", "images")[n.value]
+
     def check_finite(self):
         """Synchronises the current stream; raises PyzError (code E_NAN) if a step since the last check produced a
         NaN / Inf loss."""

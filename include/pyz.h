@@ -295,6 +295,12 @@ int pyz_last_run_info(const pyz_mlp *mlp, int32_t *h_graph_steps, int32_t *h_eag
  * any call before it), captures again. */
 int pyz_sgld_run_info(const pyz_mlp *mlp, int32_t *h_captures);
 
+/* *h_form = where the steps of the last device-resident run on this plan (pyz_sgd_run / pyz_swag_run / pyz_sgld_run /
+ * pyz_bbb_run / pyz_adam_run / pyz_bsam_run) found their batch rows: 0 = each step gathered its own, 1 = assembled one
+ * step ahead as contiguous rows, 2 = assembled one step ahead as the two fragment-major images of DESIGN section 3
+ * (PYZ_BATCH_FRAG, input width a multiple of 8; the SGD / SWAG / SGLD / BBB runs only).  Results do not depend on it. */
+int pyz_run_batch_form(const pyz_mlp *mlp, int32_t *h_form);
+
 /* Non-finite sentinel (the reference prints the loss every step, Optimizer.py:123, so a diverged chain is
  * seen at once; here losses stay on the device): every kernel that finalises a step's loss counts NaN / Inf
  * results.  Synchronises `stream`, returns PYZ_E_NAN if any step since the last call was non-finite (the
