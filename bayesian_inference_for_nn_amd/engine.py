@@ -879,7 +879,8 @@ class ConvSpec:
     tail: MLPSpec
 
     def op_shapes(self):
-        """[(in (H, W, C), out (OH, OW, N))] per op; ValueError where a kernel or a pool does not fit its input."""
+        """[(in (H, W, C), out (OH, OW, N))] per op; ValueError where a kernel or a pool does not fit its input, or a
+        filter has more taps than the kernels' tap table holds."""
         h, w, c = (int(d) for d in self.input_shape)
         out = []
         for k, op in enumerate(self.ops):
@@ -888,6 +889,8 @@ class ConvSpec:
                 ph, pw = (kh - 1, kw - 1) if pad == "same" else (0, 0)
                 if kh > h + ph or kw > w + pw:
                     raise ValueError(f"op {k}: a {kh} x {kw} kernel is larger than the padded {h + ph} x {w + pw} image")
+                if kh * kw * c > CONV_MAX_K:
+                    raise ValueError(f"op {k}: {kh * kw * c} taps per filter exceed {CONV_MAX_K}")
                 o = (h + ph - kh + 1, w + pw - kw + 1, int(f))
             else:
                 _, ph, pw = op

@@ -292,7 +292,7 @@ class ConvNet(DenseNet):
     Anything else raises a ValueError that names the layer and the field."""
 
     def __init__(self, model_config: str):
-        from ..engine import ConvSpec
+        from ..engine import CONV_MAX_K, ConvSpec
         cfg = json.loads(model_config) if isinstance(model_config, str) else model_config
         if cfg.get("class_name") != "Sequential":
             raise ValueError("only Keras Sequential models are supported")
@@ -343,6 +343,9 @@ class ConvNet(DenseNet):
                 if kh > shape[0] + ph or kw > shape[1] + pw:
                     raise ValueError(f"{what}: kernel_size ({kh}, {kw}) is larger than the padded "
                                      f"{shape[0] + ph} x {shape[1] + pw} image")
+                if kh * kw * shape[2] > CONV_MAX_K:
+                    raise ValueError(f"{what}: kernel_size ({kh}, {kw}) over {shape[2]} channels is {kh * kw * shape[2]} taps "
+                                     f"per filter, more than the {CONV_MAX_K} the kernels hold")
                 layer = ConvLayer(cn, c, (kh, kw, shape[2], int(filters)))
                 layer._dense_index = n_weight
                 n_weight += 1

@@ -14,6 +14,10 @@ Written in NumPy from the definitions, not from the kernels:
 
 WRONG names restatements that are wrong in one way each; tests/test_conv_host.py shows that the comparisons used on the
 GPU tell each of them from the right one.  torch-CPU autograd pins the right one there (this module does not use torch).
+
+The last section restates the host rules that launch the conv kernels (waves per tile, rows per weight-gradient range,
+the chunk walk, the tile counts) and names, in LAUNCH_CELLS, the paths they open; tests/test_conv_dispatch_table.py pins
+both to the source and to the cases.
 """
 
 from __future__ import annotations
@@ -29,7 +33,9 @@ MARGIN = 1e-5       # the generator keeps every ReLU pre-activation and every po
 
 WRONG = ("kernel read as (cout, cin, kh, kw)", "extra same pad on top / left", "pool gradient to the last maximum",
          "remainder row pooled", "conv bias gradient dropped", "Flatten in CHW order", "act' of the wrong layer after a pool",
-         "labels not gathered by row_idx")
+         "labels not gathered by row_idx", "no act' between two adjacent convs", "data gradient cropped at the bottom / right pad")
+# the last two apply to none of A-T (wrong_applies): until H and I no case had a conv directly on a conv, or a data gradient
+# through a padded conv
 
 
 # ---------------------------------------------------------------- the cases
@@ -85,11 +91,26 @@ CASES = {c.name: c for c in (
              "even kernel with same padding: the extra zero row / column is on the bottom / right"),
     ConvCase("T", (7, 7, 2), (("conv", 4, (1, 1), "valid", "linear"), ("pool", (3, 3))), (2,), ("softmax",), (5,),
              "exact ties inside pool windows: the first maximum wins", ties=True),
+    # the launch paths no case above reaches (LAUNCH_CELLS below names the cell each of these is the only one to reach)
+    ConvCase("H", (6, 5, 3), (("conv", 16, C3, "same", "tanh"), ("conv", 33, C3, "same", "relu")), (3,), ("softmax",), (7,),
+             "a conv on a conv: dgrad times tanh' of the conv below, with pt = pl = 1; K = 144: 73 steps over four waves "
+             "(19 / 18 / 18 / 18); 5 k tiles x 2 column tiles in the weight-gradient reduce, the second column tile ragged"),
+    ConvCase("I", (5, 4, 2), (("conv", 3, (2, 2), "same", "relu"), ("conv", 4, (2, 2), "same", "tanh")), (2,), ("linear",), (6,),
+             "dgrad through the asymmetric pad of an even same kernel (pt = pl = 0, the zeros at the bottom / right); relu' "
+             "of the conv below"),
+    ConvCase("J", (2, 23, 89), (("conv", 3, (2, 23), "valid", "tanh"),), (2,), ("softmax",), (33,),
+             "K = 4094, the limit: KT = 4096, the full tap table, S = 4 forward, 128 k tiles in the reduce, a ragged second "
+             "row tile"),
+    ConvCase("K", (2, 3, 2), (("conv", 3, (5, 5), "same", "tanh"),), (2,), ("linear",), (5,),
+             "a same kernel larger than its map: most taps of every row fall outside the image"),
 )}
 TABLE = ("A", "B", "C", "D", "E", "F")      # the six cases the feature was specified with
-ALL = TABLE + ("G", "T")
-P_CASES = ("A", "C")                         # also run with three particles
+OLD = TABLE + ("G", "T")                     # the cases the feature shipped with
+NEW = ("H", "I", "J", "K")
+ALL = OLD + NEW
+P_CASES = ("A", "C", "H")                    # also run with three particles
 EXTRA_ROWS = 4                               # images of the data set outside every batch
+PLAN_SLACK = 3                               # the GPU tests' plans have max_batch = batch + PLAN_SLACK
 
 
 # ---------------------------------------------------------------- the restatement
@@ -165,7 +186,7 @@ def forward(spec, theta, x, wrong=None):
             xp = np.pad(h, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
             z = np.einsum("byxcij,ijcn->byxn", _windows(xp, kh, kw), W) + b
             out = _act(z, act)
-            tape.append(dict(kind="conv", x=h, xp=xp, z=z, h=out, W=W, pads=(pt, pl), act=act, k=(kh, kw)))
+            tape.append(dict(kind="conv", x=h, xp=xp, z=z, h=out, W=W, pads=(pt, pl), pads_br=(pb, pr), act=act, k=(kh, kw)))
             h = out
         else:
             _, ph, pw = op
@@ -232,14 +253,24 @@ def loss_grad(spec, theta, x, y, wrong=None):
         d = d @ L["W"].T
         if li > 0:
             d = d * _act_grad(f["dense"][li - 1]["h"], f["dense"][li - 1]["act"])
+    grad = np.concatenate([stem_grad(f, d, wrong, spec.acts[0])] + blocks[::-1]).astype(dt)
+    assert grad.shape == theta.shape
+    return loss, grad, f["features"], f["out"]
+
+
+def stem_grad(f, dfeat, wrong=None, above_act="linear"):
+    """The stem's block of the gradient (every conv's kernel then bias, in network order) from f = forward(...) and
+    dfeat (B, F) = d loss / d features.  above_act: the activation of the first Dense layer (one WRONG reads it)."""
+    dt = dfeat.dtype
+    B = len(dfeat)
     ms = f["map_shape"]
-    d = d.reshape(B, ms[3], ms[1], ms[2]).transpose(0, 2, 3, 1) if wrong == "Flatten in CHW order" else d.reshape(ms)
+    d = dfeat.reshape(B, ms[3], ms[1], ms[2]).transpose(0, 2, 3, 1) if wrong == "Flatten in CHW order" else dfeat.reshape(ms)
     tape = f["tape"]
-    above_act = spec.acts[0]      # the activation of the weight layer above the op at hand (for one WRONG)
+    blocks = []
     for ti in range(len(tape) - 1, -1, -1):
         t = tape[ti]
         if t["kind"] == "conv":
-            if ti == len(tape) - 1 or tape[ti + 1]["kind"] == "conv":
+            if ti == len(tape) - 1 or (tape[ti + 1]["kind"] == "conv" and wrong != "no act' between two adjacent convs"):
                 d = d * _act_grad(t["h"], t["act"])        # (below a pool, the pool's backward has applied it)
             kh, kw = t["k"]
             dW = np.einsum("byxcij,byxn->ijcn", _windows(t["xp"], kh, kw), d)
@@ -251,7 +282,7 @@ def loss_grad(spec, theta, x, y, wrong=None):
                 for i in range(kh):
                     for j in range(kw):
                         dxp[:, i:i + OH, j:j + OW, :] += d @ t["W"][i, j].T
-                pt, pl = t["pads"]
+                pt, pl = t["pads_br"] if wrong == "data gradient cropped at the bottom / right pad" else t["pads"]
                 H, Wd = t["x"].shape[1:3]
                 d = dxp[:, pt:pt + H, pl:pl + Wd, :]
             above_act = t["act"]
@@ -282,9 +313,7 @@ def loss_grad(spec, theta, x, y, wrong=None):
             if wrong == "act' of the wrong layer after a pool":
                 act = "linear" if above_act == "softmax" else above_act
             d = dx * _act_grad(below["h"], act)
-    grad = np.concatenate(blocks[::-1]).astype(dt)
-    assert grad.shape == theta.shape
-    return loss, grad, f["features"], f["out"]
+    return np.concatenate(blocks[::-1]).astype(dt)
 
 
 def wrong_applies(case: ConvCase, wrong: str, gathered: bool = True) -> bool:
@@ -311,6 +340,10 @@ def wrong_applies(case: ConvCase, wrong: str, gathered: bool = True) -> bool:
         return False
     if wrong == "labels not gathered by row_idx":
         return gathered
+    if wrong == "no act' between two adjacent convs":       # (a linear conv below has act' = 1: nothing to skip)
+        return any(a[0] == "conv" and b[0] == "conv" and a[4] != "linear" for a, b in zip(case.stem, case.stem[1:]))
+    if wrong == "data gradient cropped at the bottom / right pad":      # a conv with something below it and unequal pads
+        return any(op[0] == "conv" and op[3] == "same" and (op[2][0] % 2 == 0 or op[2][1] % 2 == 0) for op in case.stem[1:])
     raise KeyError(wrong)
 
 
@@ -526,3 +559,168 @@ def margin_of(name: str, batch: int, theta) -> float:
     """_margins of the case's batch at the weights theta (float64)."""
     d = make(name, batch)
     return _margins(d.case.spec(), np.asarray(theta, dtype=np.float64), d.x[d.idx].astype(np.float64), d.case.ties)
+
+
+# ---------------------------------------------------------------- the launch rules, restated (pyz_api.hip / pyz_conv.h)
+# tests/test_conv_dispatch_table.py compares each of these with the source text; the probe reports kernel names only, so
+# this arithmetic is what ties a case to the path it takes.
+CONV_WAVES, WGRAD_CHUNK, CONV_MAX_K, CONV_MAX_ROWS = 4, 512, 4094, 1 << 24
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def conv_waves(tiles, steps):
+    S = 1
+    while S < CONV_WAVES and tiles * S < 1024 and steps >= 16 * S:
+        S *= 2
+    return S
+
+
+def rows_per_range(max_batch, OH, OW):
+    m_max = max_batch * OH * OW
+    return max(256, ((m_max + 255) // 256 + 1) // 2 * 2)
+
+
+def wave_steps(steps, S):
+    """The steps of each of the S waves: wave w takes steps w, w + S, ..."""
+    return [(steps - w + S - 1) // S for w in range(S)]
+
+
+def chunk_walk(M, rows_per_g):
+    """[[rows of each chunk] per range] of k_conv_wgrad's walk over M rows."""
+    out = []
+    for m0 in range(0, M, rows_per_g):
+        m1 = min(M, m0 + rows_per_g)
+        out.append([min(WGRAD_CHUNK, m1 - c0) for c0 in range(m0, m1, WGRAD_CHUNK)])
+    return out
+
+
+@dataclass(frozen=True)
+class ConvLaunch:
+    """What the launch code derives for one conv layer of a plan at one batch (one particle unless P is given)."""
+    layer: int               # index among the ops
+    M: int
+    K: int
+    KT: int
+    fwd_tiles: int           # k_conv_fwd: row tiles x column tiles
+    fwd_S: int
+    fwd_steps: tuple         # per wave
+    k_tiles: int             # k_conv_wgrad / the reduce: tiles over the K + 1 rows of [dW; db]
+    n_tiles: int
+    rows_per_g: int
+    G: int
+    wgrad_S: int
+    chunks: tuple            # chunk_walk
+    reduce_blocks: int
+    dgrad: bool              # k_conv_dgrad is launched (something is below)
+    below: bool              # ... with the conv below's output for act'
+    pads: tuple              # (pt, pb, pl, pr)
+    kernel: tuple
+    in_map: tuple            # (H, W, C)
+    out_map: tuple           # (OH, OW, N)
+    fwd_lds: int
+    wgrad_lds: int
+
+
+def conv_launches(shape, ops, batch, max_batch, P=1):
+    """[ConvLaunch] per conv op of the stem `ops` (ConvCase.ops form) on a plan of max_batch at `batch`."""
+    h, w, c = shape
+    out = []
+    for o, op in enumerate(ops):
+        if op[0] == "pool":
+            h, w = h // op[1], w // op[2]
+            continue
+        _, n, kh, kw, padding, _ = op
+        (pt, pb), (pl, pr) = _pads(kh, padding, None), _pads(kw, padding, None)
+        OH, OW = h + pt + pb - kh + 1, w + pl + pr - kw + 1
+        K = kh * kw * c
+        KT = (K + 2) & ~1
+        M = batch * OH * OW
+        n_tiles, k_tiles = cdiv(n, 32), cdiv(K + 1, 32)
+        fwd_tiles = cdiv(M, 32) * n_tiles
+        fwd_S = conv_waves(fwd_tiles * P, KT // 2)
+        rpg = rows_per_range(max_batch, OH, OW)
+        G = cdiv(M, rpg)
+        wg_S = conv_waves(k_tiles * n_tiles * G * P, min(M, rpg) // 2)
+        out.append(ConvLaunch(o, M, K, KT, fwd_tiles, fwd_S, tuple(wave_steps(KT // 2, fwd_S)), k_tiles, n_tiles, rpg, G, wg_S,
+                              tuple(tuple(r) for r in chunk_walk(M, rpg)), cdiv((K + 1) * n, 16), o > 0,
+                              o > 0 and ops[o - 1][0] == "conv", (pt, pb, pl, pr), (kh, kw), (h, w, c), (OH, OW, n),
+                              KT * 8 + (fwd_S * 4096 if fwd_S > 1 else 0), (wg_S * 4096 if wg_S > 1 else 0) + WGRAD_CHUNK * 16))
+        h, w, c = OH, OW, n
+    return out
+
+
+# the dedicated shapes of tests/test_gpu_conv_paths.py: name -> (input, stem, units, acts, max_batch, batches)
+PATH_SHAPES = {
+    "a1": ((32, 32, 1), (("conv", 2, C3, "same", "tanh"),), (3,), ("softmax",), 130, (5, 130)),
+    "a2": ((33, 33, 1), (("conv", 2, C3, "valid", "tanh"),), (3,), ("softmax",), 200, (3,)),
+    "b": ((63, 65, 1), (("conv", 2, C3, "same", "tanh"),), (2,), ("linear",), 4097, (4097,)),
+}
+
+
+def path_case(name):
+    shape, stem, units, acts, max_batch, batches = PATH_SHAPES[name]
+    return ConvCase(name, shape, stem, units, acts, batches, "a dedicated shape of tests/test_gpu_conv_paths.py"), max_batch
+
+
+LAUNCH_CELLS = frozenset(
+    [f"fwd S = {s}" for s in (1, 2, 4)] + [f"wgrad S = {s}" for s in (1, 2, 4)] +
+    ["k tiles > 1", "column tiles > 1", "k tiles > 1 and column tiles > 1", "G = 1", "1 < G <= 16", "G > 16",
+     "one chunk a range", "several chunks a range", "last chunk even", "last chunk odd", "last chunk of at most one step a wave",
+     "several chunks a range where OW < W", "dgrad with below", "dgrad without below", "dgrad pad 0", "dgrad pad symmetric",
+     "dgrad pad asymmetric", "kernel larger than the map", "K = PYZ_CONV_MAX_K", "the last image ends at PYZ_CONV_MAX_ROWS"])
+# the cell each new case and each dedicated shape is the only one to reach (asserted by tests/test_conv_dispatch_table.py)
+OWNED = {"H": "k tiles > 1 and column tiles > 1", "I": "dgrad pad asymmetric", "J": "K = PYZ_CONV_MAX_K",
+         "K": "kernel larger than the map", "a1": "last chunk of at most one step a wave",
+         "a2": "several chunks a range where OW < W", "b": "the last image ends at PYZ_CONV_MAX_ROWS"}
+
+
+def launch_cells(L: ConvLaunch):
+    """The cells of LAUNCH_CELLS one conv layer at one batch reaches.  The three `last chunk` cells speak of the last chunk
+    of a range of several chunks: of a single chunk `rows` is all there is, and every case of the table has one."""
+    cells = {f"fwd S = {L.fwd_S}", f"wgrad S = {L.wgrad_S}"}
+    if L.k_tiles > 1:
+        cells.add("k tiles > 1")
+    if L.n_tiles > 1:
+        cells.add("column tiles > 1")
+    if L.k_tiles > 1 and L.n_tiles > 1:
+        cells.add("k tiles > 1 and column tiles > 1")
+    cells.add("G = 1" if L.G == 1 else "1 < G <= 16" if L.G <= 16 else "G > 16")
+    for r in L.chunks:
+        if len(r) == 1:
+            cells.add("one chunk a range")
+            continue
+        cells.add("several chunks a range")
+        cells.add("last chunk odd" if r[-1] % 2 else "last chunk even")
+        if r[-1] <= 2 * L.wgrad_S:
+            cells.add("last chunk of at most one step a wave")
+        if L.out_map[1] < L.in_map[1]:      # the window's corner is then no linear function of the row number
+            cells.add("several chunks a range where OW < W")
+    if L.dgrad:
+        pt, pb, pl, pr = L.pads
+        cells.add("dgrad with below" if L.below else "dgrad without below")
+        cells.add("dgrad pad 0" if not any(L.pads) else "dgrad pad symmetric" if (pt, pl) == (pb, pr) else "dgrad pad asymmetric")
+    if L.kernel[0] > L.in_map[0] or L.kernel[1] > L.in_map[1]:
+        cells.add("kernel larger than the map")
+    if L.K == CONV_MAX_K:
+        cells.add("K = PYZ_CONV_MAX_K")
+    if L.M > CONV_MAX_ROWS - L.out_map[0] * L.out_map[1]:
+        cells.add("the last image ends at PYZ_CONV_MAX_ROWS")
+    return cells
+
+
+def reached_cells(name):
+    """The cells a case of CASES (at its batches, on the GPU tests' plan of batch + PLAN_SLACK) or a dedicated shape reaches."""
+    if name in PATH_SHAPES:
+        case, max_batch = path_case(name)
+        runs = [(b, max_batch) for b in case.batches]
+    else:
+        case = CASES[name]
+        runs = [(b, b + PLAN_SLACK) for b in case.batches]
+    cells = set()
+    for b, mb in runs:
+        for L in conv_launches(case.shape, case.ops, b, mb):
+            cells |= launch_cells(L)
+    return cells

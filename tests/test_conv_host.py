@@ -1,7 +1,8 @@
 """Conv models on the host: the parser and the flat layout, every refusal, the C-ABI's argument errors, and the float64
 restatement of tests/conv_checks.py pinned three ways -- against torch-CPU float64 autograd on every GPU case (1e-10), by a
-float32 stand-in that must lie four times inside the GPU tests' bound, and by eight wrong restatements that the GPU
-tests' comparison must tell from the right one.  No GPU."""
+float32 stand-in that must lie four times inside the GPU tests' bound, and by ten wrong restatements that the GPU
+tests' comparison must tell from the right one -- and the limits of the kernels (taps per filter, rows per launch), each
+refused by name on one side and accepted on the other.  No GPU."""
 
 import ctypes
 import json
@@ -183,6 +184,47 @@ def test_stem_argument_errors_do_not_need_a_gpu():
         _lib.check(rc)
 
 
+def test_limits_are_refused_by_name_and_their_neighbours_are_not():
+    """The tap limit and the row limit, each from both sides.  pyz_stem_create checks shapes before it looks for a device:
+    an accepted shape gets as far as the device (or, with one, to a plan), a refused one stops with the limit's name.  On
+    the GPU case J (K = 4094) and the 2^24 - 1 rows of tests/test_gpu_conv_paths.py run the accepted neighbours."""
+    from bayesian_inference_for_nn_amd import _lib, engine
+    header = open(_lib._build.CSRC + "/pyz_conv.h").read()
+    assert f"#define PYZ_CONV_MAX_K {engine.CONV_MAX_K} " in header and engine.CONV_MAX_K == cc.CONV_MAX_K == 4094
+    assert "#define PYZ_CONV_MAX_ROWS (1 << 24) " in header and cc.CONV_MAX_ROWS == 1 << 24
+
+    def outcome(shape, ops, max_batch):
+        lib, rc, h, msg = _stem_create(shape, ops, max_batch)
+        if h.value is not None:
+            lib.pyz_stem_destroy(h)
+        return rc, msg
+    # K = 3 * 3 * 455 = 4095 is one tap too many; 2 * 23 * 89 = 4094 (case J) is not
+    rc, msg = outcome((3, 3, 455), [(0, 2, 3, 3, 0, 1)], 4)
+    assert rc == -2 and "op 0: 4095 taps per filter exceed 4094" in msg
+    rc, msg = outcome((2, 23, 89), [(0, 3, 2, 23, 0, 2)], 36)
+    assert rc == 0 or "no HIP device" in msg, (rc, msg)
+    # 4098 images of the 63 x 65 map are 16 781 310 rows, 4097 are 16 777 215 = 2^24 - 1
+    rc, msg = outcome((63, 65, 1), [(0, 2, 3, 3, 1, 2)], 4098)
+    assert rc == -2 and "op 0: max_batch 4098 x the 63 x 65 x 2 map exceeds the kernels' row or index range" in msg
+    assert 4097 * 63 * 65 == cc.CONV_MAX_ROWS - 1 < cc.CONV_MAX_ROWS < 4098 * 63 * 65
+    # a same kernel larger than its map is a model (case K), a valid one is not
+    assert ConvSpec((2, 3, 2), (("conv", 3, 5, 5, "same", "tanh"),), cc.CASES["K"].spec().tail).features == 18
+    lib, rc, h, msg = _stem_create((2, 3, 2), [(0, 3, 5, 5, 0, 2)])
+    assert rc == -2 and "larger than the padded" in msg
+
+
+def test_python_surface_refuses_too_many_taps_by_layer():
+    from bayesian_inference_for_nn_amd.engine import ConvPlan, MLPSpec
+    with pytest.raises(ValueError, match="op 0: 4095 taps per filter exceed 4094"):
+        ConvPlan(ConvSpec((3, 3, 455), (("conv", 2, 3, 3, "valid", "relu"),), MLPSpec((2, 2), ("softmax",))), max_batch=4)
+    with pytest.raises(ValueError) as e:
+        model_from_json(conv_sequential_json((3, 3, 455), [("conv", 2, 3, "valid", "relu")], (2,), ("softmax",)))
+    assert "Conv2D" in str(e.value) and "kernel_size" in str(e.value) and "4095" in str(e.value) and "4094" in str(e.value)
+    # the neighbour parses: 4094 taps
+    net = model_from_json(conv_sequential_json((2, 23, 89), [("conv", 3, (2, 23), "valid", "tanh")], (2,), ("softmax",)))
+    assert net.spec.conv_shapes() == [(2, 23, 89, 3)] and net.spec.features == 3
+
+
 def test_plan_refuses_a_tail_that_does_not_fit_before_it_needs_a_device():
     from bayesian_inference_for_nn_amd.engine import ConvPlan, MLPSpec
     with pytest.raises(ValueError, match="features"):
@@ -325,8 +367,40 @@ def test_wrong_restatements_fail_the_gpu_comparison(wrong):
     assert applied >= 1, wrong
 
 
-def test_at_least_eight_wrong_restatements():
-    assert len(set(cc.WRONG)) >= 8
+def test_at_least_ten_wrong_restatements():
+    assert len(set(cc.WRONG)) >= 10
+
+
+def test_the_two_new_wrong_restatements_apply_to_no_old_case():
+    """The gap the rows H and I close, written down: a data gradient without the act' of the conv below, or cropped at the
+    wrong pad, passed every comparison of the eight cases the feature shipped with."""
+    no_act, crop = "no act' between two adjacent convs", "data gradient cropped at the bottom / right pad"
+    assert no_act in cc.WRONG and crop in cc.WRONG
+    assert [n for n in cc.ALL if cc.wrong_applies(cc.CASES[n], no_act)] == ["H", "I"]
+    assert [n for n in cc.ALL if cc.wrong_applies(cc.CASES[n], crop)] == ["I"]
+    for name in cc.OLD:       # where it does not apply the wrong restatement is the right one, bit for bit
+        d = cc.make(name, cc.CASES[name].batches[-1])
+        for wrong in (no_act, crop):
+            _, grad, _, _ = cc.loss_grad(d.case.spec(), d.theta[0].astype(np.float64), d.x[d.idx].astype(np.float64), d.y[d.idx],
+                                         wrong=wrong)
+            assert np.array_equal(grad, cc.reference(name, cc.CASES[name].batches[-1])[1]), (name, wrong)
+
+
+def test_stem_grad_is_the_stem_half_of_loss_grad():
+    """cc.stem_grad from the feature gradient the Dense layer sends down is the stem's block of cc.loss_grad (which the
+    torch pin above covers): the reference of the stem-only GPU tests."""
+    for name in ("C", "H"):
+        batch = cc.CASES[name].batches[-1]
+        d = cc.make(name, batch)
+        spec = d.case.spec()
+        theta = d.theta[0].astype(np.float64)
+        f = cc.forward(spec, theta, d.x[d.idx].astype(np.float64))
+        W, _ = cc.unpack(spec, theta)[-1]
+        delta = f["out"].copy()
+        delta[np.arange(batch), d.y[d.idx]] -= 1.0
+        g = cc.stem_grad(f, (delta / batch) @ W.T)
+        ref = cc.reference(name, batch)[1]
+        assert g.shape == (spec.stem_params,) and np.abs(g - ref[:spec.stem_params]).max() <= 1e-14 * np.abs(ref).max()
 
 
 # ---------------------------------------------------------------- the training task of the end-to-end GPU test

@@ -1,6 +1,8 @@
 """Conv models on the GPU: the stem's kernels (k_conv_fwd, k_conv_wgrad + k_conv_wgrad_reduce, k_conv_dgrad, k_pool_fwd,
 k_pool_bwd) and the conv-net entry points against the float64 restatement of tests/conv_checks.py, at the smallest shapes
-at which each kernel can still go wrong (the table in conv_checks.CASES), then SGD / SWAG / BayesianModel end to end.
+at which each kernel can still go wrong (the table in conv_checks.CASES: A-T as the feature shipped, H-K for the launch
+paths those do not reach -- tests/test_conv_dispatch_table.py ties each to its path), then SGD / SWAG / BayesianModel end to
+end.  tests/test_gpu_conv_paths.py holds the paths that need a shape of their own.
 
 Tolerance: 1e-4 of the reference block's largest magnitude, per layer block, for features, loss,
 gradient and step increment."""
@@ -50,7 +52,7 @@ def upload_x(x, off_by_four=False):
     return t
 
 
-def plan_of(case, batch, particles=1, slack=3):
+def plan_of(case, batch, particles=1, slack=cc.PLAN_SLACK):      # (the launch arithmetic of conv_checks.reached_cells counts on it)
     from bayesian_inference_for_nn_amd.engine import ConvPlan
     return ConvPlan(case.spec(), max_batch=batch + slack, max_particles=particles)
 
