@@ -78,6 +78,10 @@ SIGNATURES = {
     "pyz_bbb_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int, _f, _f, _f, _f, _p, _p, _i64, _u64, _p, _p, _p]),
     "pyz_bbb_run": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, _f, _f, _f, _p, _p, _i64,
                               _i64, _u64, _p, _p, _p, _p, C.c_int, _p, C.c_int, _p]),
+    "pyz_bbb_lanes_step": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, _p, C.c_int, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                                     C.POINTER(_f), _p, _p, _i64, _u64, C.c_int, _p, _p, _p]),
+    "pyz_bbb_lanes_run": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f),
+                                    _p, _p, _p, C.POINTER(_i32), C.c_int, _i64, _i64, _u64, C.c_int, _p, _p]),
     "pyz_adam_run": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.POINTER(_i64), C.c_int, C.c_double,
                                C.c_double, _f, _f, C.c_int, _f, _f, _i64, _i64, _u64, _p, C.c_int, _p]),
     "pyz_bsam_run": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(_i32), C.POINTER(_f), C.c_int, C.c_double, C.c_double,

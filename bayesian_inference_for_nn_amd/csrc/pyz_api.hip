@@ -24,6 +24,7 @@
 #include "pyz_rng.h"
 #include "pyz_sgld_chains.h"
 #include "pyz_sgld_lanes.h"
+#include "pyz_bbb_lanes.h"
 #include "pyz_members.h"
 
 namespace {
@@ -2368,6 +2369,134 @@ int pyz_bbb_run(pyz_mlp *m, float *d_mu, float *d_rho, float *d_w, const float *
   bc.val_losses = d_val_losses;
   return sgld_run_impl(m, d_mu, d_rho, d_w, d_x, d_y, d_row_idx, h_batch_sizes, h_lr, n_steps, step0, slot0, seed, d_costs,
                        use_graph, stream, PYZ_UPD_BBB, nullptr, &bc);
+}
+
+// ---- BBB lanes (pyz_bbb_lanes.h): n_lanes posteriors that differ by lr, alpha and their scalar prior, as the rows of one
+// particle-batched step.  Launch order: k_bbb_sample_lanes, the gradient pass of the SGLD rows step (PYZ_UPD_NONE into the
+// plan's (P, D) gradient buffer, per-particle losses in the plan's scalars), k_loss_finalize when the head is not fused,
+// k_bbb_update_lanes.
+static int bbb_lanes_check(const pyz_mlp *m, const void *mu, const void *rho, const void *w, int P, const void *x, const void *y,
+                           const void *h_lr, const void *h_alpha, const void *h_pm, const void *h_pr, const void *pm_vec,
+                           const void *pr_vec, int64_t step, int seed_stride, const void *cost) {
+  if (P < 1) return pyz_fail(PYZ_E_INVALID, "n_lanes %d: at least one lane", P);
+  if (step < 0) return pyz_fail(PYZ_E_INVALID, "negative step count");
+  if (seed_stride != 0 && seed_stride != 1)
+    return pyz_fail(PYZ_E_INVALID, "seed_stride %d: 0 (one noise stream for every lane) or 1 (seed + lane)", seed_stride);
+  if (!mu || !rho || !w || !x || !y || !h_lr || !h_alpha || !h_pm || !h_pr || !cost) return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if ((pm_vec == nullptr) != (pr_vec == nullptr))
+    return pyz_fail(PYZ_E_INVALID, "prior vectors: both the mean and the rho vector, or neither");
+  if (P > PYZ_MAX_LANES) return pyz_fail(PYZ_E_SHAPE, "n_lanes %d outside [1, %d] of the library", P, PYZ_MAX_LANES);
+  if (!m) return pyz_fail(PYZ_E_INVALID, "null plan");
+  if (P > m->max_p) return pyz_fail(PYZ_E_SHAPE, "n_lanes %d outside [1, %d] of the plan", P, m->max_p);
+  return check_loss_combo(m);
+}
+
+struct BbbLanes {   // what a lanes step needs beside the plan and the batch
+  float *mu, *rho, *w;
+  int P;
+  const float *h_lr, *h_alpha, *h_pm, *h_pr;   // host, [P] each
+  const float *pm_vec, *pr_vec;
+  uint64_t seed;
+  int seed_stride;
+};
+
+static void launch_bbb_lanes_step(pyz_mlp *m, const BbbLanes &b, const float *x, const void *y, const int32_t *row_idx,
+                                  int grid_batch, int slot, bool chained, long long row_stride, int64_t step,
+                                  const float *eps, float *cost, hipStream_t st) {
+  const StepCtl *ctl = m->ctl + slot;
+  const int P = b.P;
+  BbbLanesArgs a{};
+  a.mu = b.mu;
+  a.rho = b.rho;
+  a.w = b.w;
+  a.grad = m->grad;
+  a.D = m->D;
+  a.grad_pstride = m->D;
+  a.groups = (m->D + 3) / 4;
+  a.nblk = cdiv(cdiv(m->D, 4), 256);
+  a.pm_vec = b.pm_vec;
+  a.pr_vec = b.pr_vec;
+  a.seed = b.seed;
+  a.seed_stride = (unsigned)b.seed_stride;
+  a.step = (uint32_t)step;
+  a.chained = chained ? 1 : 0;
+  a.eps = eps;
+  a.part_kl = full(m)->x.part2;
+  a.ploss = m->scal;
+  a.ctl = ctl;
+  a.next = chained ? m->ctl + (slot ^ 1) : nullptr;
+  a.tab_bs = m->tab_bs;
+  a.tab_lr = m->tab_lr;
+  a.row_stride = row_stride;
+  a.cost = cost;
+  a.nonfinite = m->nonfinite;
+  for (int c = 0; c < P; ++c) {
+    a.tab.lr[c] = b.h_lr[c];
+    a.tab.alpha[c] = b.h_alpha[c];
+    a.tab.prior_mean[c] = b.h_pm[c];
+    a.tab.prior_rho[c] = b.h_pr[c];
+  }
+  const dim3 grid = sgld_rows_grid(a.groups, P);
+  PYZ_LAUNCH(k_bbb_sample_lanes, grid, dim3(256), 0, st, a);
+  WgradArgs u{};
+  u.mode = PYZ_UPD_NONE;
+  u.grad = m->grad;
+  u.grad_pstride = m->D;
+  const bool fused = can_fuse(m);
+  if (fused) u.ploss = m->scal;
+  launch_loss_backward(m, b.w, m->D, P, x, y, row_idx, grid_batch, ctl, true, u, st);
+  if (!fused) PYZ_LAUNCH(k_loss_finalize, dim3(P), dim3(64), 0, st, m->part, m->cur_nblk, ctl, m->scal, m->nonfinite);
+  PYZ_LAUNCH(k_bbb_update_lanes, grid, dim3(256), 0, st, a);
+}
+
+int pyz_bbb_lanes_step(pyz_mlp *m, float *d_mu, float *d_rho, float *d_w, int n_lanes, const float *d_x, const void *d_y,
+                       const int32_t *d_row_idx, int batch, const float *h_lr, const float *h_alpha, const float *h_prior_mean,
+                       const float *h_prior_rho, const float *d_prior_mean_vec, const float *d_prior_rho_vec, int64_t step,
+                       uint64_t seed, int seed_stride, const float *d_eps, float *d_cost, void *stream) {
+  int rc = bbb_lanes_check(m, d_mu, d_rho, d_w, n_lanes, d_x, d_y, h_lr, h_alpha, h_prior_mean, h_prior_rho, d_prior_mean_vec,
+                           d_prior_rho_vec, step, seed_stride, d_cost);
+  if (rc) return rc;
+  if ((rc = check_call(m, n_lanes, batch))) return rc;
+  if ((rc = need_grad(m, n_lanes))) return rc;
+  if ((rc = need_part2(m, (size_t)n_lanes * cdiv(cdiv(m->D, 4), 256)))) return rc;
+  hipStream_t st = as_stream(stream);
+  set_ctl_lazy(m, batch, h_lr[0], step);   // the first kernel of the gradient pass carries the step scalars
+  const BbbLanes b{d_mu, d_rho, d_w, n_lanes, h_lr, h_alpha, h_prior_mean, h_prior_rho, d_prior_mean_vec, d_prior_rho_vec,
+                   seed, seed_stride};
+  launch_bbb_lanes_step(m, b, d_x, d_y, d_row_idx, batch, 0, false, 0, step, d_eps, d_cost, st);
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
+}
+
+// The run on the skeleton of sgld_rows_run: every step enqueued for its own batch size (pyz_last_run_info reports eager
+// steps), the StepCtl ping-pong advanced by lane 0 of the update kernel, nothing synchronises inside the call.  The
+// lanes' numbers hold for every step of the call; the device's rate table gets lane 0's lr (nobody reads it).  There is
+// no validation forward inside the run.
+int pyz_bbb_lanes_run(pyz_mlp *m, float *d_mu, float *d_rho, float *d_w, int n_lanes, const float *d_x, const void *d_y,
+                      const float *h_lr, const float *h_alpha, const float *h_prior_mean, const float *h_prior_rho,
+                      const float *d_prior_mean_vec, const float *d_prior_rho_vec, const int32_t *d_row_idx,
+                      const int32_t *h_batch_sizes, int n_steps, int64_t step0, int64_t slot0, uint64_t seed, int seed_stride,
+                      float *d_costs, void *stream) {
+  int rc = bbb_lanes_check(m, d_mu, d_rho, d_w, n_lanes, d_x, d_y, h_lr, h_alpha, h_prior_mean, h_prior_rho, d_prior_mean_vec,
+                           d_prior_rho_vec, step0, seed_stride, d_costs);
+  if (rc) return rc;
+  if (!d_row_idx || !h_batch_sizes) return pyz_fail(PYZ_E_INVALID, "null pointer");
+  if ((rc = check_run(m, n_steps, slot0, h_batch_sizes)) < 0) return rc;
+  if ((rc = need_grad(m, n_lanes))) return rc;
+  if ((rc = need_part2(m, (size_t)n_lanes * cdiv(cdiv(m->D, 4), 256)))) return rc;
+  hipStream_t st = as_stream(stream);
+  const long long row_stride = m->max_batch;
+  const std::vector<float> lane0((size_t)n_steps, h_lr[0]);
+  if ((rc = upload_run_tables(m, h_batch_sizes, lane0.data(), n_steps, step0, slot0, nullptr, d_x, d_row_idx, 0, st))) return rc;
+  m->run_graph_steps = m->run_eager_steps = m->run_graph_launches = 0;
+  const BbbLanes b{d_mu, d_rho, d_w, n_lanes, h_lr, h_alpha, h_prior_mean, h_prior_rho, d_prior_mean_vec, d_prior_rho_vec,
+                   seed, seed_stride};
+  for (int s = 0; s < n_steps; ++s) {
+    launch_bbb_lanes_step(m, b, d_x, d_y, d_row_idx, h_batch_sizes[s], s & 1, true, row_stride, step0 + s, nullptr, d_costs, st);
+    ++m->run_eager_steps;
+  }
+  PYZ_LAUNCH_CHECK();
+  return PYZ_OK;
 }
 
 // ---------------------------------------------------------------- ADAM / VADAM / BSAM train loops, device resident

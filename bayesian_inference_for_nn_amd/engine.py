@@ -574,6 +574,64 @@ class MLPPlan(_NetPlan):
                                    int(slot0), int(seed), ptr(costs_out), val_plan.h if val_plan is not None else None,
                                    ptr(val_x), ptr(val_y), n_val, ptr(val_losses_out), 1 if use_graph else 0, _stream()))
 
+    def _check_bbb_lanes(self, mu, rho, w, lrs, alphas, prior_means, prior_rhos, seed_stride, prior_mean_vec, prior_rho_vec):
+        """The (n_lanes, D) state, the four host tables (P floats each) and the shared prior vectors of BBB lanes; returns
+        (P, the tables as float32 arrays)."""
+        P = int(mu.shape[0]) if mu.dim() == 2 else 0
+        if not 1 <= P <= min(self.max_particles, _lib.MAX_LANES):
+            raise ValueError(f"mu must be (n_lanes, {self.D}) with 1 <= n_lanes <= {min(self.max_particles, _lib.MAX_LANES)}")
+        for t, nm in ((mu, "mu"), (rho, "rho"), (w, "w")):
+            _f32(t, (P, self.D), nm)
+        if seed_stride not in (0, 1):
+            raise ValueError("seed_stride must be 0 (one noise stream for every lane) or 1 (seed + lane)")
+        if (prior_mean_vec is None) != (prior_rho_vec is None):
+            raise ValueError("prior_mean_vec and prior_rho_vec go together")
+        for t, nm in ((prior_mean_vec, "prior_mean_vec"), (prior_rho_vec, "prior_rho_vec")):
+            if t is not None:
+                _f32(t, (self.D,), nm)
+        return P, [self._lane_rates(v, (P,)) for v in (lrs, alphas, prior_means, prior_rhos)]
+
+    def bbb_lanes_step(self, mu, rho, w, x, y, lrs, alphas, prior_means, prior_rhos, step, seed, cost_out, seed_stride=0,
+                       batch=None, row_idx=None, eps=None, prior_mean_vec=None, prior_rho_vec=None):
+        """bbb_step for the n_lanes rows of mu / rho / w (n_lanes, D) on ONE shared batch: lane c with lrs[c], alphas[c] and
+        the scalar prior (prior_means[c], prior_rhos[c]) (P host floats each; or the shared (D,) prior vectors), and the
+        seed seed + c * seed_stride (or row c of the (n_lanes, D) eps); cost_out: float32 (n_lanes, 4)."""
+        P, tabs = self._check_bbb_lanes(mu, rho, w, lrs, alphas, prior_means, prior_rhos, seed_stride, prior_mean_vec,
+                                        prior_rho_vec)
+        if eps is not None:
+            _f32(eps, (P, self.D), "eps")
+        _f32(cost_out, name="cost_out")
+        if cost_out.numel() < 4 * P:
+            raise ValueError("cost_out must hold 4 * n_lanes entries")
+        batch = int(batch if batch is not None else (row_idx.numel() if row_idx is not None else x.shape[0]))
+        self._check_xy(x, y, row_idx, batch)
+        fp = C.POINTER(C.c_float)
+        check(self.lib.pyz_bbb_lanes_step(self.h, ptr(mu), ptr(rho), ptr(w), P, ptr(x), ptr(y), ptr(row_idx), batch,
+                                          *[t.ctypes.data_as(fp) for t in tabs], ptr(prior_mean_vec), ptr(prior_rho_vec),
+                                          int(step), int(seed), int(seed_stride), ptr(eps), ptr(cost_out), _stream()))
+
+    def bbb_lanes_run(self, mu, rho, w, x, y, row_idx, batch_sizes: Sequence[int], lrs, alphas, prior_means, prior_rhos,
+                      step0, seed, costs_out, seed_stride=0, slot0=0, prior_mean_vec=None, prior_rho_vec=None):
+        """n = len(batch_sizes) steps of bbb_lanes_step without host work in between (see sgld_chains_run; the lanes' four
+        tables hold for every step); costs_out: float32 (slots, n_lanes, 4), step s writes row slot0 + s."""
+        P, tabs = self._check_bbb_lanes(mu, rho, w, lrs, alphas, prior_means, prior_rhos, seed_stride, prior_mean_vec,
+                                        prior_rho_vec)
+        n_steps = len(batch_sizes)
+        if n_steps < 1:
+            raise ValueError("at least one step")
+        self._check_xy(x, y, row_idx, 1)
+        _f32(costs_out, name="costs_out")
+        if slot0 < 0 or row_idx.numel() < (slot0 + n_steps) * self.max_batch or costs_out.numel() < 4 * P * (slot0 + n_steps):
+            raise ValueError("row_idx / costs_out too small")
+        if any(int(b) < 1 or int(b) > self.max_batch for b in batch_sizes):
+            raise ValueError("batch size outside the plan")
+        bs = (C.c_int32 * n_steps)(*[int(b) for b in batch_sizes])
+        fp = C.POINTER(C.c_float)
+        check(self.lib.pyz_bbb_lanes_run(self.h, ptr(mu), ptr(rho), ptr(w), P, ptr(x), ptr(y),
+                                         *[t.ctypes.data_as(fp) for t in tabs], ptr(prior_mean_vec), ptr(prior_rho_vec),
+                                         ptr(row_idx), bs, n_steps, int(step0), int(slot0), int(seed), int(seed_stride),
+                                         ptr(costs_out), _stream()))
+
     def _run_tables(self, row_idx, batch_sizes, lrs, losses_out, slot0, per_step=1):
         """The argument checks the chained runs share (see sgd_run); returns the host tables as ctypes arrays."""
         n_steps = len(batch_sizes)

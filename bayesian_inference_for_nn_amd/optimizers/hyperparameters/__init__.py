@@ -1,4 +1,4 @@
 from .HyperParameters import HyperParameters
 from .space import Parameter, Number, Real, Integer, Constant
 from .HyperparameterOptimizer import HyperparameterOptimizer
-from .GridOptimizer import GridOptimizer, SGLDGridObjective
+from .GridOptimizer import GridOptimizer, SGLDGridObjective, BBBGridObjective

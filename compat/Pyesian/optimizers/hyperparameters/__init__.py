@@ -1,2 +1,2 @@
 from bayesian_inference_for_nn_amd.optimizers.hyperparameters import (  # noqa: F401
-    Constant, GridOptimizer, HyperParameters, HyperparameterOptimizer, Integer, Number, Parameter, Real, SGLDGridObjective)
+    BBBGridObjective, Constant, GridOptimizer, HyperParameters, HyperparameterOptimizer, Integer, Number, Parameter, Real, SGLDGridObjective)

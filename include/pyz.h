@@ -344,6 +344,36 @@ int pyz_bbb_run(pyz_mlp *mlp, float *d_mu, float *d_rho, float *d_w, const float
                 pyz_mlp *val_plan, const float *d_val_x, const void *d_val_y, int n_val,
                 float *d_val_losses, int use_graph, void *stream);
 
+/* ---- BBB lanes: n_lanes Bayes-by-Backprop posteriors that differ by their hyper-parameters (the points of a grid search
+ * side by side).  pyz_bbb_step for the n_lanes rows of d_mu / d_rho / d_w (n_lanes, D) on ONE shared batch: lane c steps
+ * with h_lr[c] and h_alpha[c] against the scalar prior (h_prior_mean[c], softplus(h_prior_rho[c])) -- HOST floats, [n_lanes]
+ * each: they ride in the launch -- or against the per-element vectors d_prior_mean_vec / d_prior_rho_vec (D, shared by
+ * the lanes; both or neither), and draws eps from the Philox seed seed + c * seed_stride (seed_stride = 0: ONE stream for
+ * every lane, 1: the stream of a single pyz_bbb_step with seed + c) or takes row c of d_eps (n_lanes, D).  Lane c's
+ * {cost, data loss, log q - log p, 0} go to d_cost[4 c ..].  A lane's sampled weights and its log q - log p are the bits
+ * pyz_bbb_step gives from the same mu, rho, eps and prior; the same call gives the same bits.
+ * PYZ_E_INVALID, with no device touched: a null plan, a null pointer among the required ones, n_lanes < 1, a negative
+ * step, seed_stride outside {0, 1}, exactly one of the two prior vectors.  PYZ_E_SHAPE: n_lanes above the plan's
+ * max_particles or above PYZ_MAX_LANES. */
+int pyz_bbb_lanes_step(pyz_mlp *mlp, float *d_mu, float *d_rho, float *d_w, int n_lanes, const float *d_x, const void *d_y,
+                       const int32_t *d_row_idx, int batch, const float *h_lr, const float *h_alpha,
+                       const float *h_prior_mean, const float *h_prior_rho /* host, [n_lanes] each */,
+                       const float *d_prior_mean_vec, const float *d_prior_rho_vec /* (D) shared, or NULL */,
+                       int64_t step, uint64_t seed, int seed_stride, const float *d_eps /* (n_lanes, D) or NULL */,
+                       float *d_cost /* (n_lanes, 4) */, void *stream);
+
+/* n_steps steps of pyz_bbb_lanes_step without host work in between: d_row_idx (slots, max_batch) / h_batch_sizes as for
+ * pyz_sgld_run, the lanes' four host tables hold for every step of the call, step i is optimizer step step0 + i (its
+ * Philox step) and writes its (n_lanes, 4) costs to row slot0 + i of d_costs.  Every step is enqueued for its own batch
+ * size (no hipGraph: pyz_last_run_info reports eager steps), nothing synchronises inside the call, there is no validation
+ * forward, and the results equal n_steps calls of pyz_bbb_lanes_step bit for bit. */
+int pyz_bbb_lanes_run(pyz_mlp *mlp, float *d_mu, float *d_rho, float *d_w, int n_lanes, const float *d_x, const void *d_y,
+                      const float *h_lr, const float *h_alpha, const float *h_prior_mean,
+                      const float *h_prior_rho /* host, [n_lanes] each */, const float *d_prior_mean_vec,
+                      const float *d_prior_rho_vec /* (D) shared, or NULL */, const int32_t *d_row_idx,
+                      const int32_t *h_batch_sizes, int n_steps, int64_t step0, int64_t slot0, uint64_t seed,
+                      int seed_stride, float *d_costs /* (slots, n_lanes, 4) */, void *stream);
+
 /* The ADAM / VADAM train loop (ADAM.step / VADAM.step inside Optimizer.train, ADAM.py:42-86, VADAM.py:45-99,
  * Optimizer.py:121-134) as ONE device-resident run of n_steps steps, replayed from captured hipGraphs like pyz_sgld_run:
  * d_row_idx (slots, max_batch) / h_batch_sizes / h_lr / slot0 as there.  h_epochs[s] (>= 1) is the epoch count step s uses
